@@ -8,7 +8,15 @@ A "step" is one MeshIntegrator::step with exactly AdmmIter = 10 ADMM iterations 
 disabled, SURVEY §8d protocol); value = ADMM iterations per second over the timed steps.  The
 first warm-up step (finite-difference Hessians) is reported separately.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run does what the headline needs and no more: set-up, W warm-up steps, K timed steps, the
+outputs of the last timed step to DIR/<name>.npy when --dump-outputs is given, and the result line.
+--full adds every other section (early-exit run, copy ceiling, SpMV and CG-STAB, backward Euler, C2,
+BFGS-heavy, 3D, the CPU baselines), each of which can still be dropped with its --no-* option.
+One engine takes at most --engine-steps steps (48, warm-up included): C3's trajectory ends in a
+non-finite prox energy at its 55th step from the initial mesh.  A longer run goes on with a fresh
+engine, set up and warmed up from the initial mesh while the clock is stopped, so K timed steps are
+K steady steps of the first 48 of the trajectory (`engine_restarts` in the line counts the engines).
 N > 1 runs N ranks, one per GPU: under a launcher (torch.distributed.run, WORLD_SIZE = N) directly,
 otherwise bench.py re-launches itself under torch.distributed.run before anything touches the GPU
 (fewer than N visible GPUs, or WORLD_SIZE != N: exit status 2, no line).  The global mesh grows with N (hexagonal disc of
@@ -21,7 +29,7 @@ C3-sized meshes.
 The second half of the metric, achieved HBM GB/s in SpMV, is measured on the backward-Euler
 Jacobian CSR of the 2D SquareGrid n=707 mesh (n = 2,002,226 rows, nnz = 28,008,516, SURVEY §8d
 microbenchmark ii) with the LASolver replacement's matmult, and reported under "spmv" together
-with one ILU(0)-preconditioned CG-STAB solve of that matrix.
+with one ILU(0)-preconditioned CG-STAB solve of that matrix (--full).
 """
 import argparse
 import json
@@ -49,6 +57,16 @@ def parse():
                          "the N-rank path on a box with fewer GPUs, not a measurement)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other section: the early-exit run, the copy ceiling, "
+                         "SpMV/CG-STAB, backward Euler, C2, BFGS-heavy, 3D and the CPU baselines (minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (energy, ADMM iterations run, node positions) as "
+                         "DIR/<name>.npy in float64, at most 64 MB in all (a seeded row sample of a larger array)")
+    ap.add_argument("--engine-steps", type=int, default=48,
+                    help="steps one engine takes, warm-up included, before the timed steps go on with a fresh engine "
+                         "warmed up from the initial mesh, the clock stopped meanwhile (C3's 55th step from the "
+                         "initial mesh ends in a non-finite energy)")
     ap.add_argument("--admm-iter", type=int, default=10)
     ap.add_argument("--disc-n", type=int, default=577)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -773,6 +791,29 @@ def lib_provenance(mx):
             "lib_matches_tree": tree is not None and tree == info.get("src_hash")}
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files of a run together
+DUMP_SEED = 20221015
+
+
+def dump_outputs(path, arrays, budget):
+    """--dump-outputs: every array as path/<name>.npy in float64.  Arrays that together exceed
+    `budget` bytes are cut to a fixed sample of their rows (sorted row ids drawn without replacement
+    from numpy's PCG64 seeded with DUMP_SEED, the same for every run of the same shapes), each to its
+    share of the budget; the row ids go to path/<name>_rows.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget and a.ndim == 2:
+            # ids are stored as float64 beside the rows: 8 bytes more per row
+            keep = int(budget * (a.nbytes / total) // (a.shape[1] * 8 + 8))
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], size=keep, replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def pmc_flops(kernel):
     """Executed fp64 flops per launch from the SQ_INSTS_VALU_{ADD,MUL,FMA,TRANS}_F64 pass."""
     return pmc_entry(kernel).get("fp64_flops_per_launch")
@@ -857,30 +898,41 @@ def main():
             dist.broadcast_object_list(uid, src=0)
             comm = mx.Comm.rccl(world, rank, uid[0], local, timeout_s=args.comm_timeout)
         phase("engine")
-        eng = mx.Engine(M, dt, rank=rank, nranks=world, comm=comm)
         # ncclCommCount for RCCL; the host transport only knows the count it was made with
         comm_nranks = comm.nranks()
         rccl_nranks = None if host_comm else comm_nranks
         if comm_nranks != world:
             raise RuntimeError("communicator has %d ranks, expected %d" % (comm_nranks, world))
-    else:
-        eng = mx.Engine(M, dt)
-    if c5:
-        eng.set_regrid(True)  # the monitor grid rebuilt on the device at every step start
+
+    def make_engine():
+        e = mx.Engine(M, dt, rank=rank, nranks=world, comm=comm) if world > 1 else mx.Engine(M, dt)
+        if c5:
+            e.set_regrid(True)  # the monitor grid rebuilt on the device at every step start
+        return e
+
+    eng = make_engine()
     t_setup = time.perf_counter() - t_setup
     log(f"rank {rank}: setup {t_setup:.1f}s, local nodes {eng.nP}, local simplices {eng.nF}")
     if world > 1:
         phase("setup")
         phase("warmup")
 
+    n_warm = max(args.warmup, 1)
+    life = max(args.engine_steps, n_warm + 1)  # steps one engine takes, its warm-up included
     first_ms = None
-    for w in range(max(args.warmup, 1)):
-        t0 = time.perf_counter()
-        eng.step(args.admm_iter, -1.0)
-        if w == 0:
-            first_ms = (time.perf_counter() - t0) * 1e3
-    eng.set_timing(True)
-    eng.reset_stats()
+
+    def warm_up(e):
+        nonlocal first_ms
+        for w in range(n_warm):
+            t0 = time.perf_counter()
+            e.step(args.admm_iter, -1.0)
+            if first_ms is None:
+                first_ms = (time.perf_counter() - t0) * 1e3
+        e.set_timing(True)
+        e.reset_stats()
+        return n_warm
+
+    taken = warm_up(eng)  # steps the current engine has taken
 
     def barrier():
         if world > 1:
@@ -888,16 +940,40 @@ def main():
 
     if world > 1:
         phase("timed")
-    barrier()
-    torch.cuda.synchronize()
-    eng.sync()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        eng.step(args.admm_iter, -1.0)
-    eng.sync()
-    torch.cuda.synchronize()
-    barrier()
-    elapsed = time.perf_counter() - t0
+    # The trajectory is a finite resource: at C3 the 55th step from the initial mesh ends in a
+    # non-finite prox energy (error 7, no inverted element; the same step on every run).  So the timed
+    # steps run in segments: an engine takes at most `life` steps, then a fresh one is set up and
+    # warmed up from the initial mesh with the clock stopped.  --steps up to life - warmup: one segment.
+    elapsed, left, restarts, last = 0.0, args.steps, 0, None
+    seg_stats = []
+    while left > 0:
+        if taken >= life:
+            seg_stats.append(eng.stats())
+            eng.close()
+            eng = make_engine()
+            taken = warm_up(eng)
+            restarts += 1
+        n = min(left, life - taken)
+        barrier()
+        torch.cuda.synchronize()
+        eng.sync()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            last = eng.step(args.admm_iter, -1.0)
+        eng.sync()
+        torch.cuda.synchronize()
+        barrier()
+        elapsed += time.perf_counter() - t0
+        left -= n
+        taken += n
+    if args.dump_outputs and last is not None:
+        # what the last timed step handed its caller: the energy, the ADMM iterations it ran and the
+        # node positions (a partitioned rank holds its own nodes: one set of files per rank)
+        import numpy as np
+        sfx = "_rank%d" % rank if world > 1 else ""
+        dump_outputs(args.dump_outputs,
+                     {"energy" + sfx: np.array([last[0]]), "admm_iters" + sfx: np.array([last[1]]),
+                      "x" + sfx: eng.get("x").reshape(eng.nP, eng.dim)}, DUMP_BUDGET_BYTES // world)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if host_comm else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -906,6 +982,9 @@ def main():
     if world > 1:
         phase("report")
     st = eng.stats()
+    for k in ("t_prox_ms", "n_prox", "t_xupdate_ms", "n_xupdate", "t_exchange_ms", "n_exchange", "bfgs_iters",
+              "admm_iters"):  # the counters and timers of every segment; the rest as the last engine has it
+        st[k] += sum(e[k] for e in seg_stats)
     # per rank: local nodes and simplices, the halo exchange's device time per ADMM iteration (pack +
     # send/recv on its stream, overlapped with the interior x-update), its bytes, the interior nodes
     mine = (eng.nP, eng.nF, (st["t_exchange_ms"] * 1e3 / st["n_exchange"]) if st["n_exchange"] else None,
@@ -914,11 +993,17 @@ def main():
     if world > 1:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
-    # a second run with the early exit enabled reports the iterations actually executed
-    eng.reset_stats()
-    for _ in range(3):
-        eng.step(args.admm_iter, 1e-3)
-    st_early = eng.stats()
+    st_early = None
+    if args.full:
+        # a second run with the early exit enabled reports the iterations actually executed
+        if taken + 3 > life:
+            eng.close()
+            eng = make_engine()
+            taken = warm_up(eng)
+        eng.reset_stats()
+        for _ in range(3):
+            eng.step(args.admm_iter, 1e-3)
+        st_early = eng.stats()
     iters = args.steps * args.admm_iter
     # whole-job throughput: C5 is one fixed mesh (strong scaling); C3/C4 in units of the
     # single-GPU mesh (the global mesh grows with the ranks: weak scaling)
@@ -942,6 +1027,9 @@ def main():
         "ranks": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
+        "engine_steps": life,
+        "engine_restarts": restarts,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "higher_is_better": True,
         "scaling": "strong" if c5 else "weak",
@@ -984,8 +1072,8 @@ def main():
         "kernels": {"k_prox_ms": round(prox_ms, 4), "k_xupdate_ms": round(xup_ms, 4),
                     "k_xupdate_GBs": round(xup_gbs, 1), "bfgs_iters_per_prox":
                         round(st["bfgs_iters"] / max(st["admm_iters"], 1) / mesh.nF, 4)},
-        "early_exit": {"tol": 1e-3, "steps": 3,
-                       "admm_iters_per_step": round(st_early["admm_iters"] / 3, 2)},
+        "early_exit": (None if st_early is None else
+                       {"tol": 1e-3, "steps": 3, "admm_iters_per_step": round(st_early["admm_iters"] / 3, 2)}),
         "first_step_ms": round(first_ms, 2),
         "setup_s": round(t_setup, 2),
         "build": lib_provenance(mx),
@@ -1004,28 +1092,28 @@ def main():
         result["roofline"]["frac_compulsory"] = round(comp / (prox_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
         result["roofline"]["compulsory_note"] = ("bytes_per_launch minus the prox-entry gradient cache "
                                                  "(16 K B per simplex, K = 6)")
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         cc, tc = stream_copy_ceiling(torch, la)
         result["roofline"]["measured_copy_ceiling_GBs"] = cc
         result["roofline"]["torch_copy_GBs"] = tc
         result["roofline"]["frac_of_copy_ceiling"] = round(prox_gbs / cc, 4)
-    if not args.no_spmv and not c4:
+    if args.full and not args.no_spmv and not c4:
         log("spmv microbenchmark")
         result["spmv"] = spmv_bench(torch, la, mx, with_cpu=(rank == 0 and world == 1 and not args.no_cpu_baseline))
-    if not args.no_be and world == 1 and not c4:
+    if args.full and not args.no_be and world == 1 and not c4:
         log("backward Euler")
         result["backward_euler"] = be_bench(mx, with_cpu=not args.no_cpu_baseline)
     threads = cpu_threads(args)
-    if not args.no_c2 and world == 1 and not c4:
+    if args.full and not args.no_c2 and world == 1 and not c4:
         log("C2 square grid")
         result["c2"] = c2_bench(mx, not args.no_cpu_baseline, threads, args.admm_iter)
-    if not args.no_bfgs and world == 1 and not c4:
+    if args.full and not args.no_bfgs and world == 1 and not c4:
         log("BFGS-heavy 2D (rho 1)")
         try:
             result["bfgs_heavy"] = bfgs_bench(mx, not args.no_cpu_baseline, threads, args.admm_iter)
         except Exception as e:  # noqa: BLE001 -- reported in the line, the headline stands
             result["bfgs_heavy"] = {"error": str(e)}
-    if not args.no_3d and world == 1 and not c4:
+    if args.full and not args.no_3d and world == 1 and not c4:
         log("3D C4")
         result["c4_3d"] = c4_bench(mx, not args.no_cpu_baseline, threads, args.admm_iter)
         log("3D time-varying monitor")
@@ -1039,7 +1127,7 @@ def main():
     if args.c5 and world == 1 and rank == 0:
         log("3D C5 time-varying (5.09 M nodes)")
         result["c5_time_varying"] = tv_bench(mx, 136, args.admm_iter, steps=2)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not c4:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not c4:
         log("cpu baseline")
         result["cpu_baseline"] = cpu_baseline(mesh, args.admm_iter, threads, steps1=CPU_STEPS)
     for f in DEFERRED:  # the sections' CPU baselines, after every GPU measurement

@@ -12,7 +12,7 @@ the uncorrected figure.
          profiles/r05/pmc/write_counter_collection.csv.gz profiles/r05/pmc/f64_counter_collection.csv.gz \
          bfgs_heavy=profiles/r05/pmc/f64b_counter_collection.csv.gz
 
-(round 5, as round 4: each pass is its own rocprofv3 run of `bench.py --steps 10 --warmup 2 --no-cpu-baseline
+(round 5, as round 4: each pass is its own rocprofv3 run of `bench.py --full --steps 10 --warmup 2 --no-cpu-baseline
 --no-bfgs`, dev/r5_final_pmc.sh; the f64 pass of the BFGS-heavy section alone is profiles/r04/bfgs_only.py;
 the summary holds only the kernels those runs launched)
 

@@ -2,7 +2,7 @@ set -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out/r4final
 mkdir -p $O
-B="bench.py --steps 10 --warmup 2 --no-cpu-baseline"
+B="bench.py --full --steps 10 --warmup 2 --no-cpu-baseline"
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE -f csv -d $O/fetch -o run -- python3 $B --no-bfgs > /dev/null 2> $O/fetch.err || exit $?
 timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE -f csv -d $O/write -o run -- python3 $B --no-bfgs > /dev/null 2> $O/write.err || exit $?
 timeout -s KILL 300 rocprofv3 --pmc SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 -f csv -d $O/f64 -o run -- python3 $B --no-bfgs > /dev/null 2> $O/f64.err || exit $?

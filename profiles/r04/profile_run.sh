@@ -8,7 +8,7 @@ cd "$(dirname "$0")/../.."
 export TMPDIR=/tmp
 O=gpurun_out/r4prof
 mkdir -p $O
-B="bench.py --steps 10 --warmup 2 --no-cpu-baseline"
+B="bench.py --full --steps 10 --warmup 2 --no-cpu-baseline"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d $O/kt -o run -- python3 $B > $O/bench_under_rocprof.json 2> $O/kt.err || exit $?
 timeout -s KILL 400 rocprofv3 --pmc FETCH_SIZE -f csv -d $O/fetch -o run -- python3 $B --no-bfgs > /dev/null 2> $O/fetch.err || exit $?
 timeout -s KILL 400 rocprofv3 --pmc WRITE_SIZE -f csv -d $O/write -o run -- python3 $B --no-bfgs > /dev/null 2> $O/write.err || exit $?

@@ -2,7 +2,7 @@
 gather form (MMX_XUP_TILE=0): x-update and prox kernel times and ADMM it/s from bench.py's C3 line,
 alternating; run from the repository root."""
 import json, os, subprocess, sys
-B = [sys.executable, "-u", "bench.py", "--steps", "20", "--warmup", "3", "--no-spmv", "--no-be", "--no-bfgs",
+B = [sys.executable, "-u", "bench.py", "--full", "--steps", "20", "--warmup", "3", "--no-spmv", "--no-be", "--no-bfgs",
      "--no-3d", "--no-cpu-baseline"]
 for rep in range(2):
     for tile in ("1", "0"):

@@ -10,6 +10,12 @@ Cases: Jacobian patterns of 2D SquareGrid n=4 and n=9 and 3D n=
 shifted random values (converging in a few iterations), a hard case that needs hundreds of
 iterations, one that does not converge within nitmax, an initial guess with new_rhat = 1, a zero
 right-hand side (the reference returns NaN, 0/0 in alpha), and the tridiagonal probe (ILU(0) exact).
+
+tests/golden/lasolver_seeded/reference_outputs.npz holds the reference's outputs alone for the
+seeded systems that tests/test_lasolver_oracle.py and tests/test_lasolver_host.py draw themselves
+(seeded_system / seeded_pattern below are their generators): the packed pattern, the solve and
+the ILU(0) factor of three mesh Jacobians, and the level 1-3 symbolic factors of six random
+unsymmetric patterns.
 """
 import os
 import sys
@@ -93,6 +99,63 @@ def make_levels():
     np.savez_compressed(os.path.join(OUT, "ilu_levels.npz"), **out)
 
 
+SEEDED = os.path.join(HERE, "lasolver_seeded", "reference_outputs.npz")
+LIVE_SEEDS = (11, 12, 13)
+PATTERN_SEEDS = tuple(range(6))
+PATTERN_LEVELS = (1, 2, 3)
+
+
+def seeded_system(seed):
+    """(N, rows, cols, values of a packed pattern, right-hand side) of a 2D SquareGrid Jacobian"""
+    rng = np.random.default_rng(seed)
+    m = oracle_py.Mesh.rect(2, 5 + seed % 3)
+    rows, cols = L.mesh_entries(2, m.F)
+    N = 2 * m.nP
+    return N, rows, cols, (lambda ia, ja: L.random_values(ia, ja, seed, 0.2 + 0.3 * (seed % 2))), rng.uniform(-1, 1, N)
+
+
+def seeded_pattern(seed):
+    """(n, rows, cols) of a random unsymmetric pattern with a full diagonal"""
+    rng = np.random.default_rng(seed)
+    n = int(rng.integers(20, 200))
+    rows, cols = [], []
+    for i in range(n):
+        c = set(rng.integers(0, n, int(rng.integers(1, 8))).tolist()) | {i}
+        rows += [i] * len(c)
+        cols += sorted(c)
+    return n, np.array(rows, np.int32), np.array(cols, np.int32)
+
+
+def reference_seeded(seed):
+    """the reference's pack, solve and ILU(0) factor of seeded_system(seed)"""
+    N, rows, cols, values, b = seeded_system(seed)
+    ia, ja = L.pack(N, rows, cols, use_ref=True)
+    a = values(ia, ja)
+    x, nitr, _ = L.solve(ia, ja, a, b, use_ref=True)
+    return {"ia": ia, "ja": ja, "x": x, "nitr": np.int32(nitr), "af": L.ref_ilu(ia, ja, a)[2]}
+
+
+def reference_symbolic(ia, ja, level):
+    """the reference's level-of-fill symbolic factor of a packed pattern"""
+    iaf, jaf = L.ref_ilu(ia, ja, np.ones(len(ja)), level)[:2]
+    return {"iaf": iaf, "jaf": jaf}
+
+
+def make_seeded():
+    out = {}
+    for seed in LIVE_SEEDS:
+        for k, v in reference_seeded(seed).items():
+            out[f"live{seed}_{k}"] = v
+    for seed in PATTERN_SEEDS:
+        n, rows, cols = seeded_pattern(seed)
+        ia, ja = L.pack(n, rows, cols)
+        for lev in PATTERN_LEVELS:
+            for k, v in reference_symbolic(np.asarray(ia), np.asarray(ja), lev).items():
+                out[f"sym{seed}_l{lev}_{k}"] = v
+    os.makedirs(os.path.dirname(SEEDED), exist_ok=True)
+    np.savez_compressed(SEEDED, **out)
+
+
 if __name__ == "__main__":
     assert L.ref_available(), "build oracle/_ref first: make -f oracle/Makefile.ref -C oracle"
     os.makedirs(OUT, exist_ok=True)
@@ -101,3 +164,5 @@ if __name__ == "__main__":
         print(f"{c[0]}: n={n} nnz={nnz} nitr={it}")
     make_levels()
     print("ilu_levels")
+    make_seeded()
+    print("lasolver_seeded")

@@ -105,7 +105,7 @@ def test_bench_two_ranks_host_transport_rehearsal():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--comm", "host", "--steps", "3",
-                        "--warmup", "1", "--disc-n", "120", "--no-cpu-baseline"], capture_output=True, text=True,
+                        "--warmup", "1", "--disc-n", "120", "--full", "--no-cpu-baseline"], capture_output=True, text=True,
                        timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -5,8 +5,9 @@ names and signatures (src/Mesh.h:22-25, src/MeshIntegrator.h:12-51, src/MonitorF
 that includes the reference's own monitor plugins Experiments/TestMonitors/MEx*.h UNCHANGED, from
 where they lie in the reference checkout (they include <Eigen/Dense>, served by
 include/mmadmm/eigen_shim, and "../../src/MonitorFunction.h", whose include guard our header
-shares).  The binary is built in-tree (tests/_build/, git-ignored) by __graft_entry__.build() or
-here, when the reference checkout is present; the GPU test runs that binary.
+shares).  The binary is built into oracle/_ref/ (git-ignored, with the other builds from the
+reference) by __graft_entry__.build() or here, when the reference checkout is present; the GPU
+test runs that binary.
 
 * CPU: every monitor of main.cpp's registry (MonType 0-5, 2D and 3D) gives a set-up grid
   bit-identical to the engine's built-in restatement of it (host only, mmadmm_monitor_grid).
@@ -27,19 +28,15 @@ from ref_runs import POINTS_ATOL, SIX_DIGITS, ih, load_txt, rel_err
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_MONITORS = "/root/reference/Experiments/TestMonitors"
 BUILD = os.path.join(ROOT, "tests", "_build")
-DRIVER = os.path.join(BUILD, "dropin_driver")
+DRIVER = os.path.join(ROOT, "oracle", "_ref", "dropin_driver")
 INC = os.path.join(ROOT, "include")
 
 
 def compile_driver():
-    """g++ the driver against include/mmadmm (+ the Eigen shim) and the reference's MEx*.h."""
-    os.makedirs(BUILD, exist_ok=True)
-    cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wno-unused-variable",
-           "-I", os.path.join(INC, "mmadmm", "eigen_shim"), "-I", os.path.join(INC, "mmadmm"), "-I", REF_MONITORS,
-           os.path.join(ROOT, "tests", "cpp", "dropin_driver.cpp"), "-o", DRIVER,
-           "-L", os.path.join(ROOT, "mm-admm_amd", "lib"), "-lmmadmm",
-           "-Wl,-rpath,$ORIGIN/../../mm-admm_amd/lib"]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    """g++ the driver against include/mmadmm (+ the Eigen shim) and the reference's MEx*.h: the
+    `dropin` target of oracle/Makefile.ref."""
+    subprocess.run(["make", "-s", "-f", "Makefile.ref", "-C", os.path.join(ROOT, "oracle"), "dropin",
+                    "MONITORS=" + REF_MONITORS], check=True, capture_output=True, text=True)
 
 
 def driver():
@@ -101,7 +98,7 @@ int main() {
 def test_dropin_driver_reproduces_monitor210(tmp_path):
     """Monitor210 (SquareGrid 10, MEx3, dt 0.025 tau 0.5 rho 1000, AdmmIter 10, DtTol 1e-4)."""
     if not os.path.exists(DRIVER):
-        pytest.skip("dropin_driver not built in-tree")
+        pytest.skip("dropin_driver not built (oracle/_ref)")
     r = subprocess.run([DRIVER, "run", "2", "10", "3", "0.025", "0.5", "1000", "10", "1000", "1e-4", str(tmp_path)],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
@@ -129,7 +126,7 @@ def test_lasolver_mirror_backward_euler_monitor220():
     digits with the same step count, and every energy and the final node positions equal the
     engine's own mmadmm_backward_euler_step run bit for bit."""
     if not os.path.exists(DRIVER):
-        pytest.skip("dropin_driver not built in-tree")
+        pytest.skip("dropin_driver not built (oracle/_ref)")
     args = [DRIVER, "be", "2", "20", "3", "0.025", "0.5", "100", "1000", "1e-4"]
     r = subprocess.run(args, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr

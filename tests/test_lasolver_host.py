@@ -11,6 +11,8 @@ import oracle_py
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(__file__)), "mm-admm_amd", "python"))
 la = pytest.importorskip("lasolver_amd")
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
+import make_lasolver_golden as G  # noqa: E402
 
 LEV = os.path.join(os.path.dirname(__file__), "golden", "lasolver", "ilu_levels.npz")
 
@@ -25,25 +27,23 @@ def test_symbolic_ilu_k_matches_reference(tag, level):
     assert np.array_equal(dg, g[f"{tag}_l{level}_diag"])
 
 
-@pytest.mark.skipif(not L.ref_available(), reason="the reference LASolver build (oracle/_ref) is not present")
-@pytest.mark.parametrize("seed", range(6))
+@pytest.mark.parametrize("seed", G.PATTERN_SEEDS)
 def test_symbolic_ilu_k_random_patterns_match_reference_build(seed):
     """Round 6: the level-of-fill symbolic factor (a heap-driven row merge, sparse.cpp) against the
-    reference's own scaler_ILU built in place (oracle/_ref) on random unsymmetric patterns, levels
-    1-3, where fill joins the pivots of its own row."""
-    rng = np.random.default_rng(seed)
-    n = int(rng.integers(20, 200))
-    rows, cols = [], []
-    for i in range(n):
-        c = set(rng.integers(0, n, int(rng.integers(1, 8))).tolist()) | {i}
-        rows += [i] * len(c)
-        cols += sorted(c)
-    ia, ja = L.pack(n, np.array(rows, np.int32), np.array(cols, np.int32))
+    reference's own scaler_ILU on random unsymmetric patterns, levels 1-3, where fill joins the
+    pivots of its own row: its factors as stored in golden/lasolver_seeded and, where the reference
+    has been built in place (oracle/_ref), as it computes them now."""
+    n, rows, cols = G.seeded_pattern(seed)
+    ia, ja = L.pack(n, rows, cols)
     ia, ja = np.asarray(ia), np.asarray(ja)
-    for level in (1, 2, 3):
+    g = np.load(G.SEEDED)
+    for level in G.PATTERN_LEVELS:
         iaf, jaf, _ = la.ilu_symbolic(ia, ja, level)
-        riaf, rjaf = L.ref_ilu(ia, ja, np.ones(len(ja)), level)[:2]
-        assert np.array_equal(iaf, riaf) and np.array_equal(jaf, rjaf), level
+        refs = [{k: g[f"sym{seed}_l{level}_{k}"] for k in ("iaf", "jaf")}]
+        if L.ref_available():
+            refs.append(G.reference_symbolic(ia, ja, level))
+        for r in refs:
+            assert np.array_equal(iaf, r["iaf"]) and np.array_equal(jaf, r["jaf"]), level
 
 
 def test_symbolic_ilu0_is_the_pattern():

@@ -1,14 +1,19 @@
 """Pins the LASolver restatement (oracle/lasolver.cpp) bit for bit: against the golden fixtures the
-reference itself produced (tests/golden/make_lasolver_golden.py) and, when the reference has been
-compiled in this container (oracle/_ref), against it on fresh seeded systems."""
+reference itself produced (tests/golden/make_lasolver_golden.py), on further seeded systems
+against its stored outputs and, when the reference has been compiled in place (oracle/_ref),
+against it directly."""
 import glob
 import os
+import sys
 
 import numpy as np
 import pytest
 
 import lasolver_py as L
 import oracle_py
+
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
+import make_lasolver_golden as G  # noqa: E402
 
 GOLD = sorted(p for p in glob.glob(os.path.join(os.path.dirname(__file__), "golden", "lasolver", "*.npz"))
               if not p.endswith("ilu_levels.npz"))
@@ -60,23 +65,24 @@ def test_mesh_pattern_equals_pack_of_buildmatrix_stream():
         assert _same(ia, ia2) and _same(ja, ja2)
 
 
-@pytest.mark.skipif(not L.ref_available(), reason="reference LASolver not built (oracle/_ref)")
-@pytest.mark.parametrize("seed", [11, 12, 13])
+@pytest.mark.parametrize("seed", G.LIVE_SEEDS)
 def test_restatement_matches_reference_live(seed):
-    rng = np.random.default_rng(seed)
-    m = oracle_py.Mesh.rect(2, 5 + seed % 3)
-    rows, cols = L.mesh_entries(2, m.F)
-    N = 2 * m.nP
-    ia, ja = L.pack(N, rows, cols, use_ref=True)
+    """Seeded systems beyond the fixtures: the reference's pack, solve and ILU(0) factor as stored in
+    golden/lasolver_seeded (tests/golden/make_lasolver_golden.py) and, where the reference has been
+    compiled (oracle/_ref), as it computes them now."""
+    N, rows, cols, values, b = G.seeded_system(seed)
+    g = np.load(G.SEEDED)
+    refs = [{k: g[f"live{seed}_{k}"] for k in ("ia", "ja", "x", "nitr", "af")}]
+    if L.ref_available():
+        refs.append(G.reference_seeded(seed))
     ia2, ja2 = L.pack(N, rows, cols)
-    assert _same(ia, ia2) and _same(ja, ja2)
-    a = L.random_values(ia, ja, seed, 0.2 + 0.3 * (seed % 2))
-    b = rng.uniform(-1, 1, N)
-    xr, nr, _ = L.solve(ia, ja, a, b, use_ref=True)
-    xo, no, _ = L.solve(ia, ja, a, b)
-    assert nr == no and _same(xr, xo)
-    _, _, afr, _ = L.ref_ilu(ia, ja, a)
-    assert _same(afr, L.ilu0(ia, ja, a))
+    a = values(ia2, ja2)
+    xo, no, _ = L.solve(ia2, ja2, a, b)
+    af = L.ilu0(ia2, ja2, a)
+    for r in refs:
+        assert _same(r["ia"], ia2) and _same(r["ja"], ja2)
+        assert int(r["nitr"]) == no and _same(r["x"], xo)
+        assert _same(r["af"], af)
 
 
 @pytest.mark.parametrize("path", GOLD, ids=[os.path.basename(p)[:-4] for p in GOLD])
