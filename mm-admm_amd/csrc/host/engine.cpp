@@ -382,11 +382,17 @@ class Engine final : public EngineBase {
     const size_t slice = maxBlocks_ * kNumPartials;
     if (deferRed && partA_.n < slice * nIters) partA_.alloc(slice * std::max(nIters, 10));
     int firstDeferred = 0;  // first iteration of the batched reduction
+    // timing: an iteration's end event is the next iteration's start event when nothing was launched
+    // between the two (one record less ahead of every prox but the first)
+    hipEvent_t prevEnd = nullptr;
     for (int i = 0; i < nIters; ++i) {
       hipEvent_t a0 = nullptr, a1 = nullptr, b1 = nullptr;
       if (timing) {
-        a0 = nextEvent();
-        MMX_HIP(hipEventRecord(a0, st_));
+        a0 = prevEnd;
+        if (!a0) {
+          a0 = nextEvent();
+          MMX_HIP(hipEventRecord(a0, st_));
+        }
       }
       const bool firstProx = !hessComputed_;          // another kernel, another partial count
       const bool swapB = prox_double_buffered(D, wave2d_) && hessComputed_;  // steady state B_ -> B2_, then swap
@@ -414,8 +420,10 @@ class Engine final : public EngineBase {
         MMX_HIP(hipEventRecord(b1, st_));
         timed_.push_back({a0, a1, b1});
       }
+      prevEnd = b1;  // cleared below by whatever is launched before the next prox
       if (deferRed) {
         if (firstProx && i < nIters - 1) {  // reduced at once: the batch below assumes one partial count
+          prevEnd = nullptr;
           launch_reduce_partials(partA_.p + slice * i, nbp, res_ + (size_t)i * 2 * kNumPartials, st_, red_);
           firstDeferred = i + 1;
         } else if (i == nIters - 1) {
@@ -424,9 +432,11 @@ class Engine final : public EngineBase {
                               res_ + (size_t)i0 * 2 * kNumPartials, st_, red_);
         }
       } else if (resid) {
+        prevEnd = nullptr;
         launch_reduce_partials2(partA_.p, nbp, res_ + (size_t)i * 2 * kNumPartials, partB_.p, nbx,
                                 res_ + (size_t)i * 2 * kNumPartials + kNumPartials, st_, red_);
       } else {
+        prevEnd = nullptr;
         launch_reduce_partials(partA_.p, nbp, res_ + (size_t)i * 2 * kNumPartials, st_, red_);
       }
       done = i + 1;
@@ -459,6 +469,14 @@ class Engine final : public EngineBase {
       bf += (long long)r[3];
       mx = std::max(mx, (int)r[5]);
     }
+#ifdef MMX_HINT_PROBE
+    {  // probe build: k_prox_lds leaves its monitor-hint hits in prox partial 2 (3 nF lookups per prox)
+      double hits = 0;
+      for (int i = 0; i < done; ++i) hits += hostRes_[(size_t)i * 2 * kNumPartials + 2];
+      fprintf(stderr, "[hint-probe] step %lld: %.0f hits of %.0f lookups in %d proxes\n", (long long)stepsTaken_, hits,
+              3.0 * nF_ * done, done);
+    }
+#endif
     const double* last = &hostRes_[(size_t)(done - 1) * 2 * kNumPartials];
     primal = sqrt(last[kNumPartials + 2]);
     dual = sqrt(last[1]);
@@ -1466,6 +1484,9 @@ class Engine final : public EngineBase {
     {
       const char* ft = getenv("MMX_FORCE_TIE");
       m.forceTie = ft ? atoi(ft) : 0;
+      const char* mh = getenv("MMX_MON_HINT");
+      m.monHint = mh ? atoi(mh) : 1;
+      if (m.monHint < 0 || m.monHint > 3) m.monHint = 1;
     }
     m.invdiag = invdiag_.p;
     m.Vc = compMesh_ ? Vc_.p : nullptr;

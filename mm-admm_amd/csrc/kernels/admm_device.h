@@ -292,9 +292,47 @@ __device__ __forceinline__ void monEval3Iso(const MonIso3& in, const double* pnt
 #pragma unroll
   for (int n = 0; n < 9; ++n) mv.m[n / 3][n % 3] = (n / 3 == n % 3) ? d : o;
 }
+// Monitor-cell hint of the 2D steady prox (k_prox_lds, isotropic grid): the cell of each vertex at
+// the workgroup's entry z and that cell's four corner values, requested under the Bkinv chunk load.
+// A vertex barely moves inside one prox, so the first blockGrad of the BFGS loop nearly always asks
+// for the same cell and interpolates from the held corners instead of gathering them after pass 1
+// (the same values in the same expressions: bit-identical); any other cell is gathered as before.
+struct MonHint2 {
+  int cell[3];   // yInd (nx + 1) + xInd of the cell the corners came from; -1: no hint
+  double v[12];  // [3][4]: its corners r0[0], r0[1], r1[0], r1[1] of evalMonitor
+#ifdef MMX_HINT_PROBE
+  mutable int hits;  // probe build: evaluations served from the hint
+#endif
+};
+// mode (DeviceMesh::monHint): 1 the vertex's own cell; 2 / 3 (test hooks) the cell one to the right /
+// one up, clamped to the grid, so nearly every evaluation misses the hint
+// (vertex by vertex with a literal index, here and in blockGrad, so the struct can be split into
+// values as soon as the calls are inlined, before the vertex loops unroll)
+__device__ __forceinline__ void monHintVertex(const GridView<2>& g, const double* z, int mode, int* cell, double* v) {
+  int xInd = findLimInf(z[0], g.ax, g.nx + 1, g.hx, g.rhx);
+  int yInd = findLimInf(z[1], g.ay, g.ny + 1, g.hy, g.rhy);
+  if (mode == 2) xInd = min(xInd + 1, g.nx - 1);
+  if (mode == 3) yInd = min(yInd + 1, g.ny - 1);
+  const int c = yInd * (g.nx + 1) + xInd;
+  const double* r0 = g.iso + c;
+  const double* r1 = r0 + (g.nx + 1);
+  *cell = c;
+  v[0] = r0[0];
+  v[1] = r0[1];
+  v[2] = r1[0];
+  v[3] = r1[1];
+}
+__device__ __forceinline__ void monHintRequest(const GridView<2>& g, const double* z, int mode, MonHint2& h) {
+  monHintVertex(g, &z[0], mode, &h.cell[0], &h.v[0]);
+  monHintVertex(g, &z[2], mode, &h.cell[1], &h.v[4]);
+  monHintVertex(g, &z[4], mode, &h.cell[2], &h.v[8]);
+}
+
 // MeshInterpolator<D>::evalMonitorOnGrid (src/MeshInterpolator.cpp:287-342)
-template <int D>
-__device__ __forceinline__ void evalMonitor(const GridView<D>& g, const double* pnt, M<D>& mv) {
+// HINT (2D): vertex hv's corners are taken from *hint when useHint and the cell is the hinted one
+template <int D, bool HINT = false>
+__device__ __forceinline__ void evalMonitor(const GridView<D>& g, const double* pnt, M<D>& mv,
+                                            const MonHint2* hint = nullptr, int hv = 0, bool useHint = false) {
   const int xInd = findLimInf(pnt[0], g.ax, g.nx + 1, g.hx, g.rhx);
   const int yInd = findLimInf(pnt[1], g.ay, g.ny + 1, g.hy, g.rhy);
   const int nx = g.nx;
@@ -319,7 +357,24 @@ __device__ __forceinline__ void evalMonitor(const GridView<D>& g, const double* 
       // formed as below, so they are bit-identical too (NaN positions included)
       const double* r0 = g.iso + (size_t)yInd * (nx + 1) + xInd;
       const double* r1 = r0 + (nx + 1);
-      const double a = r0[0], b = r0[1], e = r1[0], f = r1[1];
+      double a, b, e, f;
+      if constexpr (HINT) {
+        if (useHint && hint->cell[hv] == yInd * (nx + 1) + xInd) {
+          a = hint->v[4 * hv], b = hint->v[4 * hv + 1], e = hint->v[4 * hv + 2], f = hint->v[4 * hv + 3];
+#ifdef MMX_HINT_PROBE
+          hint->hits++;
+#endif
+        } else {
+          // gathered through global-address-space pointers (what the plain path's loads become as
+          // well): with a generic load on either side the compiler merged the two into one load
+          // through a pointer that is private or global, and the held corners went to scratch
+          typedef const __attribute__((address_space(1))) double* gptr;
+          const gptr q0 = (gptr)r0, q1 = (gptr)r1;
+          a = q0[0], b = q0[1], e = q1[0], f = q1[1];
+        }
+      } else {
+        a = r0[0], b = r0[1], e = r1[0], f = r1[1];
+      }
       const double d = c0 * a + c1 * b + c2 * e + c3 * f;
       const double o = c0 * 0.0 + c1 * 0.0 + c2 * 0.0 + c3 * 0.0;
       mv.m[0][0] = d;
@@ -426,11 +481,14 @@ __device__ __forceinline__ double pow_dp2m1(double x, bool& tie) {
 // energy a prox reports is only read for the first prox of a step, which never uses the cache.)
 // EXACT = false (prox fast path): a power too close to a rounding midpoint, or outside the
 // double-double ranges, raises *tie instead of being resolved; the results are then void.
-template <int D, bool GRAD, bool REG, bool EXACT = true>
+// HINT (2D only): the vertex monitors may come from the held cell corners *hint (MonHint2).
+template <int D, bool GRAD, bool REG, bool EXACT = true, bool HINT = false>
 __device__ __forceinline__ double blockGrad(const GridView<D>& g, const FunctionalConsts<D>& fc,
                                             const double* z, const double* xi, const double* dxpu,
                                             double* grad, double& Igt, double* ghuang = nullptr,
-                                            bool* tiep = nullptr) {
+                                            bool* tiep = nullptr, const MonHint2* hint = nullptr,
+                                            bool useHint = false) {
+  static_assert(!HINT || D == 2, "the monitor-cell hint is 2D only");
   bool tie = false;
   constexpr int K = D * (D + 1);
   const double dFact = (D == 2) ? 2.0 : 6.0;
@@ -458,9 +516,14 @@ __device__ __forceinline__ double blockGrad(const GridView<D>& g, const Function
       monEval3(ib, &z[9], mPre[3]);
     }
   }
+  if constexpr (HINT) {  // a literal vertex index (monHintVertex)
+    evalMonitor<D, true>(g, &z[0], mPre[0], hint, 0, useHint);
+    evalMonitor<D, true>(g, &z[D], mPre[1], hint, 1, useHint);
+    evalMonitor<D, true>(g, &z[2 * D], mPre[2], hint, 2, useHint);
+  }
 #pragma unroll
   for (int i = 0; i < D + 1; i++) {
-    if constexpr (!(D == 3 && MMX_MON_PIPE)) evalMonitor<D>(g, &z[i * D], mPre[i]);
+    if constexpr (!(D == 3 && MMX_MON_PIPE) && !HINT) evalMonitor<D>(g, &z[i * D], mPre[i]);
 #pragma unroll
     for (int r = 0; r < D; ++r)
 #pragma unroll

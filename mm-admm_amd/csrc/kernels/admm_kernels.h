@@ -42,6 +42,10 @@ struct DeviceMesh {
   int xupCh;              // slots requested at once per node in the sweep (8, 16, 24)
   int xupSweep;           // 3D slot-term x-update as a per-XCD sweep: workgroups per CU (0: one node per lane)
   int forceTie;           // test hook (MMX_FORCE_TIE=n): every n-th prox block takes the exact path
+  // 2D steady prox, isotropic grid (MMX_MON_HINT, default 1): the monitor cell corners of the entry z
+  // requested at workgroup entry for the first blockGrad (MonHint2).  0: off; 2, 3: test hooks, the
+  // hint taken from the cell one to the right / one up (clamped), so nearly every lookup falls back
+  int monHint;
   const int* nodeOrder;   // x-update processing order (nodes by first incident simplex) or nullptr
   // the x-update's share of that order: positions [xupLo, xupHi) (an element partition launches its
   // interior nodes, which need no remote slot, while the halo exchange runs, then the rest)

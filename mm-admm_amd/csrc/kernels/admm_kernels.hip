@@ -726,11 +726,12 @@ __device__ __forceinline__ void bfgs_update_rows(BA& B, int i, const double (&pk
 // search, <= 50 iterations, stop when ||grad||_1 < tol.  Returns the iteration count.
 // EXACT = false: the fast path; a power near a rounding midpoint raises *tie (the caller then
 // recomputes the simplex exactly) and the loop stops.
-template <int D, class BA, bool EXACT = true>
+// HINT: the first iteration's blockGrad may take its monitor corners from *hint (MonHint2).
+template <int D, class BA, bool EXACT = true, bool HINT = false>
 __device__ __forceinline__ int bfgs_iterations(BA B, const GridView<D>& g, const FunctionalConsts<D>& fc,
                                                double* z, const double* xi, const double* dx, double* G,
                                                unsigned fixedBits, double tol, bool& bad, double* gcache,
-                                               bool* tie = nullptr) {
+                                               bool* tie = nullptr, const MonHint2* hint = nullptr) {
   constexpr int K = D * (D + 1);
   constexpr int kPipe = BA::kPipe;
   int iter;
@@ -775,7 +776,7 @@ __device__ __forceinline__ int bfgs_iterations(BA B, const GridView<D>& g, const
     for (int i = 0; i < K; ++i) z[i] += pk[i];
     double G1[K], Igt;
     {
-      const double e = blockGrad<D, true, true, EXACT>(g, fc, z, xi, dx, G1, Igt, gcache, tie);
+      const double e = blockGrad<D, true, true, EXACT, HINT>(g, fc, z, xi, dx, G1, Igt, gcache, tie, hint, iter == 0);
       bad |= (e != e);
     }
     if constexpr (BA::kPipe > 0 && !EXACT) {
@@ -1076,6 +1077,11 @@ typedef double v2nt __attribute__((ext_vector_type(2)));
 #ifndef MMX_LDS_DMA
 #define MMX_LDS_DMA 0  // 1: the chunk DMA'd to LDS after the gathers (C3 prox 0.380 ms); 0: through registers, requested before them (0.370 ms)
 #endif
+#ifndef MMX_MON_HINT_BUILD
+// 2D: the monitor-cell hint (run-time switch DeviceMesh::monHint).  1: the corners held in registers
+// for the first blockGrad; 2: only touched at entry, the first blockGrad gathers them again; 0: none
+#define MMX_MON_HINT_BUILD 1
+#endif
 template <int D, int BS>
 __global__ void __launch_bounds__(BS, 2) k_prox_lds(DeviceMesh<D> m, double tol, const double* __restrict__ x,
                                                         double* __restrict__ zg, double* __restrict__ ug,
@@ -1122,6 +1128,22 @@ __global__ void __launch_bounds__(BS, 2) k_prox_lds(DeviceMesh<D> m, double tol,
 #pragma unroll
     for (int r = 0; r < NL; ++r) cv[r] = __builtin_nontemporal_load(reinterpret_cast<const v2nt*>(chunk) + tid + r * BS);
   }
+  // 2D, isotropic grid: the monitor cells of the entry z and their corners, requested here -- z was
+  // requested before the chunk and loads return in order, so this waits for z only and the corners
+  // travel under the chunk -- for the BFGS loop's first blockGrad (MonHint2)
+  constexpr bool kHint = (D == 2) && MMX_MON_HINT_BUILD == 1;
+  constexpr bool kTouch = (D == 2) && MMX_MON_HINT_BUILD == 2;  // the touch-only form (measured slower)
+  MonHint2 hint;
+#ifdef MMX_HINT_PROBE
+  hint.hits = 0;
+#endif
+  if constexpr (kHint || kTouch) {
+    if (m.giso && m.monHint > 0) {
+      monHintRequest(gridOf<D>(m), z, m.monHint, hint);
+    } else {
+      hint.cell[0] = hint.cell[1] = hint.cell[2] = -1;
+    }
+  }
   double xi[K], dxv[K];
   loadXi<D>(m, f, xi);
   gatherX<D>(x, f, dxv);
@@ -1145,6 +1167,13 @@ __global__ void __launch_bounds__(BS, 2) k_prox_lds(DeviceMesh<D> m, double tol,
 #pragma unroll
   for (int i = 0; i < K; ++i) dx[i] = dxv[i] + dx[i];  // DXpU = D x + uBar
   __syncthreads();
+  if constexpr (kTouch) {
+    // the corners are only brought into the cache: an empty consumer keeps the requests alive, and
+    // the first blockGrad gathers as before
+    if (hint.cell[0] >= 0)
+#pragma unroll
+      for (int i = 0; i < 12; ++i) asm volatile("" ::"v"(hint.v[i]));
+  }
   double pv[6] = {0, 0, 0, 0, 0, 0};
   bool tie = false;
   if (act) {
@@ -1157,7 +1186,12 @@ __global__ void __launch_bounds__(BS, 2) k_prox_lds(DeviceMesh<D> m, double tol,
     const double Ihsave = Igt;
     LdsB<K, 64> Bacc{lds + (tid >> 6) * KK * 64 + (tid & 63)};
     const int its =
-        tie ? 0 : bfgs_iterations<D, LdsB<K, 64>, false>(Bacc, g, fc, z, xi, dx, G, fixedBits, tol, bad, gc, &tie);
+        tie ? 0
+            : bfgs_iterations<D, LdsB<K, 64>, false, kHint>(Bacc, g, fc, z, xi, dx, G, fixedBits, tol, bad, gc, &tie,
+                                                            kHint ? &hint : nullptr);
+#ifdef MMX_HINT_PROBE
+    if constexpr (kHint) pv[2] = (double)hint.hits;  // probe build: the prox leaves partial 2 unused
+#endif
     double dual2 = 0.0;
 #pragma unroll
     for (int i = 0; i < K; ++i) {
