@@ -1,6 +1,6 @@
 // MatrixIter.h -- the reference's LASolver classes (lib/LASolver/MatrixIter.h:66-383,
 // SparseItUtil.h:7-11) over the C-ABI of libmmadmm.so (include/mmx_sparse.h): the ILU-preconditioned
-// CG-STAB solve runs on the MI355X.  Same namespace, class names, signatures and argument meaning, so
+// CG-STAB, ORTHOMIN or CG solve runs on the MI355X.  Same namespace, class names, signatures and argument meaning, so
 // the reference's own caller -- Mesh<D>::buildMatrix and Mesh<D>::backwardsEulerStep (src/Mesh.cpp:
 // 262-382, 1112-1341) -- compiles unchanged against this header.
 //
@@ -27,8 +27,13 @@
 // factored again, as the reference re-factors in every solve, MatrixIter.cpp:684).  Non-convergence
 // is nitr = -1, as in the reference.  Errors the reference throws as General_Exception (a bad entry,
 // a packed structure) are thrown as General_Exception here too; so are the C-ABI's other failures
-// (no GPU, an unsupported ParamIter setting: RCM ordering, drop-tolerance ILU, scaling, orthomin and
-// CG are not implemented -- the reference's only caller uses none of them, src/Mesh.cpp:264-304).
+// (no GPU, an unsupported ParamIter setting: RCM ordering, drop-tolerance ILU and pivoting are not
+// implemented).  ParamIter.iaccel selects CG-STAB (0), ORTHOMIN(north) (1) or conjugate gradients (-1);
+// iscal = 1 scales the rows by their diagonal on the device.  As the reference, solve() with
+// iaccel = -1 sets param.iscal = 0.  One visible difference: the reference's scal() rewrites a and b
+// in place, here only the device copies are scaled -- aValue() / bValue() after a scaled solve still
+// show the unscaled values, and every solve() hands them to the device again, so repeated solves
+// give the reference's results.
 // The device is mmx_device() (0 unless set).  Header-only; link with -lmmadmm.
 #ifndef MATRIX_ITER_INC
 #define MATRIX_ITER_INC
@@ -205,8 +210,9 @@ public:
     }
 
     // x = A^-1 b (initial_guess = 0: x zeroed first) or x = x0 + A^-1 (b - A x0); nitr = -1 when
-    // CG-STAB did not converge within param.nitmax
+    // the accelerator did not converge within param.nitmax
     void solve(ParamIter& param, double* x, int& nitr, const int initial_guess = 0) {
+        if (param.iaccel == -1) param.iscal = 0;  // no scaling for conjugate gradients (MatrixIter.cpp:661-665)
         const mmx_param_iter p = param.abi();
         detail::check(mmx_matrix_set_values(m_, a.data()));
         detail::check(mmx_matrix_set_rhs(m_, b.data()));
@@ -216,6 +222,13 @@ public:
     }
 
     void set_toler(const double* tol_in) { detail::check(mmx_matrix_set_toler(m_, tol_in)); }
+
+    // the row scaling factors of the last solve (a_scal; all 1.0 when it did not scale)
+    std::vector<double> get_scale(void) {
+        std::vector<double> f(n);
+        detail::check(mmx_matrix_get_scale(m_, f.data()));
+        return f;
+    }
 
     double& bValue(const int i) { return b[i]; }
     double& aValue(const int k) { return a[k]; }

@@ -1,4 +1,5 @@
-/* mmx_sparse.h -- C-ABI of the MI355X LASolver replacement (ILU-preconditioned CG-STAB on the GPU).
+/* mmx_sparse.h -- C-ABI of the MI355X LASolver replacement (ILU-preconditioned CG-STAB, ORTHOMIN
+ * and CG on the GPU).
  *
  * Drop-in for the reference's lib/LASolver as used by backward Euler.  Each
  * entry point names the reference interface it replaces:
@@ -22,12 +23,29 @@
  *   mmx_matrix_factor              scaler_ILU::factor              lib/LASolver/ILU_class.cpp:300-444
  *   mmx_matrix_ilu_solve(_device)  scaler_ILU::solve               lib/LASolver/ILU_class.cpp:447-527
  *   mmx_matrix_get_factor          rowsp[i].af (read back)         lib/LASolver/ILU_class.h:24-90
+ *   mmx_matrix_get_scale           a_scal (read back)              lib/LASolver/MatrixIter.cpp:667-680
  *   mmx_ilu_symbolic               scaler_ILU::sfac2 / merge2      lib/LASolver/ILU_class.cpp:17-295
  *
  * Supported ParamIter settings: natural order (order 0), level-of-fill ILU (drop_ilu 0) at any
- * level, no scaling (iscal 0), no pivoting, CG-STAB acceleration (iaccel 0), either rhat.  Other
- * settings return MMADMM_ERR_INVALID with a message (the reference's only caller uses exactly
- * order 0, level 0, iscal 0, iaccel 0; src/Mesh.cpp:264-304).
+ * level, no pivoting (ipiv 0); no scaling or diagonal row scaling (iscal 0 / 1); CG-STAB with either
+ * rhat (iaccel 0), ORTHOMIN(north) (iaccel 1, north >= 1) or conjugate gradients (iaccel -1, which
+ * forces iscal 0 as the reference does).  RCM ordering, drop-tolerance ILU and pivoting return
+ * MMADMM_ERR_INVALID with a message.
+ *
+ * Row scaling (iscal 1; scal(), lib/LASolver/ILU_class.cpp:904-954) acts on the matrix's device
+ * copies at the start of every such solve: row i and b[i] are multiplied by f = 1 / (a_ii + 1e-300).
+ * As the reference's a and b, the device copies stay scaled afterwards: a later mmx_matrix_matmult
+ * sees the scaled matrix, and a second scaled solve without new values scales again -- by exactly 1,
+ * or by 1 + 2^-52 in the rows where a_ii * (1 / a_ii) rounds below 1; from the third on nothing
+ * changes.  The first scaling pass over a set of values drops a numeric factor made from the
+ * unscaled values (e.g. by an earlier solve with iscal 0 or mmx_matrix_factor), so the solve factors
+ * the scaled matrix; the repeated passes keep that factor, which after the second pass can be one
+ * rounding stale in the rows rescaled by 1 + 2^-52 (it is a preconditioner only; it is redone after
+ * set_values / sfac).
+ *
+ * Dot products and norms of all three accelerators are sums of one fixed shape (DESIGN.md
+ * section LASolver), so iterates are reproducible bit for bit; against the reference's sequential
+ * sums they differ by rounding.
  *
  * Conventions: every function returns a status code of mmadmm.h (0 = ok; message via
  * mmadmm_last_error()); no exception crosses the ABI.  Host arrays are caller-owned and copied;
@@ -50,14 +68,14 @@ typedef struct mmx_param_iter {
   int level;          /* level of fill of the ILU */
   int drop_ilu;       /* 0 level-of-fill ILU (1 drop tolerance: not supported) */
   int ipiv;           /* 0 no pivoting */
-  int iscal;          /* 0 no scaling (1: not supported) */
+  int iscal;          /* 0 no scaling, 1 rows scaled by 1 / diagonal (ignored, as 0, with iaccel -1) */
   int nitmax;         /* maximum iterations */
   double resid_reduc; /* convergence when ||r|| / ||r0|| < resid_reduc */
   int info;           /* ignored (the reference's output is commented out) */
   double drop_tol;    /* ignored (drop_ilu 0) */
-  int new_rhat;       /* 0: rhat = r0; 1: rhat = (LU)^-1 r0 */
-  int iaccel;         /* 0 CG-STAB (1 orthomin, -1 CG: not supported) */
-  int north;          /* ignored (orthomin only) */
+  int new_rhat;       /* CG-STAB only: 0: rhat = r0; 1: rhat = (LU)^-1 r0 */
+  int iaccel;         /* 0 CG-STAB, 1 ORTHOMIN(north), -1 conjugate gradients */
+  int north;          /* ORTHOMIN: directions kept before a restart (>= 1); 2 north n doubles on the device */
 } mmx_param_iter;
 
 typedef struct mmx_struc_s* mmx_struc;
@@ -110,6 +128,9 @@ int mmx_matrix_ilu_solve_device(mmx_matrix m, const double* d_b, double* d_x);
 /* factor in CSR form: iaf (n+1), jaf/af (nnz of the factor), diag (n, row-relative) */
 int mmx_matrix_factor_nnz(mmx_matrix m, long long* nnzf);
 int mmx_matrix_get_factor(mmx_matrix m, int32_t* iaf, int32_t* jaf, double* af, int32_t* diag);
+/* the row scaling factors a_scal of the last solve (n doubles): 1 / (a_ii + 1e-300) after a solve
+ * with iscal 1, all 1.0 when the last solve did not scale (or before any) */
+int mmx_matrix_get_scale(mmx_matrix m, double* scal);
 int mmx_matrix_set_timing(mmx_matrix m, int on);
 int mmx_matrix_stats_get(mmx_matrix m, mmx_sparse_stats* out);
 int mmx_matrix_stats_reset(mmx_matrix m);

@@ -1,6 +1,7 @@
 // sparse.cpp -- host side of the LASolver replacement (include/mmx_sparse.h): MatrixStruc
 // packing, the symbolic ILU (level of fill, natural order) and the device-resident MatrixIter
-// whose numeric factor, sweeps, SpMV and CG-STAB run as HIP kernels (kernels/sparse_kernels.hip).
+// whose numeric factor, sweeps, SpMV and CG-STAB run as HIP kernels (kernels/sparse_kernels.hip), as
+// do ORTHOMIN, CG and the row scaling (kernels/accel_kernels.hip).
 #include <omp.h>
 
 #include <algorithm>
@@ -207,9 +208,12 @@ int spmv_version() {
 void check_params(const mmx_param_iter& p) {
   if (p.order != 0) throw Error(MMADMM_ERR_INVALID, "unsupported ParamIter.order (only natural ordering, 0)");
   if (p.drop_ilu != 0) throw Error(MMADMM_ERR_INVALID, "unsupported ParamIter.drop_ilu (only level-of-fill ILU, 0)");
-  if (p.iscal != 0) throw Error(MMADMM_ERR_INVALID, "unsupported ParamIter.iscal (only no scaling, 0)");
   if (p.ipiv != 0) throw Error(MMADMM_ERR_INVALID, "unsupported ParamIter.ipiv (only no pivoting, 0)");
-  if (p.iaccel != 0) throw Error(MMADMM_ERR_INVALID, "unsupported ParamIter.iaccel (only CG-STAB, 0)");
+  if (p.iscal != 0 && p.iscal != 1)
+    throw Error(MMADMM_ERR_INVALID, "unsupported ParamIter.iscal (0 no scaling, 1 diagonal row scaling)");
+  if (p.iaccel != 0 && p.iaccel != 1 && p.iaccel != -1)
+    throw Error(MMADMM_ERR_INVALID, "unsupported ParamIter.iaccel (0 CG-STAB, 1 ORTHOMIN, -1 CG)");
+  if (p.iaccel == 1 && p.north < 1) throw Error(MMADMM_ERR_INVALID, "ParamIter.north must be >= 1 for ORTHOMIN");
   if (p.level < 0) throw Error(MMADMM_ERR_INVALID, "ParamIter.level must be >= 0");
 }
 
@@ -291,6 +295,18 @@ struct SparseMatrix {
   DevBuf<double> d_res, d_res0, d_p, d_vbar, d_avbar, d_s, d_z, d_t, d_x, d_part, d_tmp;
   DevBuf<CgsScalars> d_sc;
   CgsScalars* h_sc = nullptr;
+  // row scaling (iscal 1): A's diagonal positions (-1: the row has none), the factors of the last
+  // scaled solve
+  DevBuf<int> d_adiag;
+  DevBuf<double> d_ascal;
+  bool allDiag = false, scaled = false;
+  long long scaledVersion = -1;  // the valVersion whose device values the scaling pass has already rewritten
+  // ORTHOMIN / CG (accel_kernels.hip): the stored directions q / Aq (north vectors of n each, from
+  // the first ORTHOMIN solve on, again when north changes), AqAq / a_mult and the dots' partials
+  DevBuf<double> d_oq, d_oaq, d_oms, d_opart;
+  int ominNorth = 0;
+  DevBuf<AccelScalars> d_asc;
+  AccelScalars* h_asc = nullptr;
   bool timing = false;
   mmx_sparse_stats stats{};
   Timer tm[4];  // spmv, sweeps, factor, whole solve
@@ -340,12 +356,29 @@ struct SparseMatrix {
     std::vector<int4> desc(nblk);
     for (int b = 0; b < nblk; ++b) desc[b] = make_int4(rb[b], rb[b + 1], ia[rb[b]], ia[rb[b + 1]]);
     d_desc.upload(desc.data(), desc.size(), st);
+    // the diagonal's position in every row of A (the first match, as scal() searches)
+    std::vector<int> adiag(n, -1);
+    int missing = 0;
+#pragma omp parallel for schedule(static) reduction(max : missing)
+    for (int i = 0; i < n; ++i) {
+      for (int k = ia[i]; k < ia[i + 1]; ++k)
+        if (ja[k] == i) {
+          adiag[i] = k;
+          break;
+        }
+      if (adiag[i] < 0) missing = 1;
+    }
+    allDiag = missing == 0;
+    d_adiag.upload(adiag.data(), adiag.size(), st);
     MMX_HIP(hipStreamSynchronize(st));
     for (DevBuf<double>* v : {&d_res, &d_res0, &d_p, &d_vbar, &d_avbar, &d_s, &d_z, &d_t, &d_x, &d_tmp}) v->alloc(n);
     d_part.alloc((size_t)std::max(nblk, vec_grid(n)) * 3);
     d_sc.alloc(1);
     MMX_HIP(hipMemsetAsync(d_sc.p, 0, sizeof(CgsScalars), st));
     MMX_HIP(hipHostMalloc((void**)&h_sc, sizeof(CgsScalars), hipHostMallocDefault));
+    d_asc.alloc(1);
+    MMX_HIP(hipMemsetAsync(d_asc.p, 0, sizeof(AccelScalars), st));
+    MMX_HIP(hipHostMalloc((void**)&h_asc, sizeof(AccelScalars), hipHostMallocDefault));
     d_ctl.alloc(16);
     MMX_HIP(hipMemsetAsync(d_ctl.p, 0, 16 * sizeof(unsigned), st));
     d_gy.alloc(2 * (size_t)n);
@@ -361,6 +394,7 @@ struct SparseMatrix {
     if (st) (void)hipStreamSynchronize(st);
     if (evSpin) (void)hipEventDestroy(evSpin);
     if (h_sc) (void)hipHostFree(h_sc);
+    if (h_asc) (void)hipHostFree(h_asc);
     if (st) (void)hipStreamDestroy(st);
   }
 
@@ -858,9 +892,98 @@ struct SparseMatrix {
     }
   }
 
-  // MatrixIter::solve (lib/LASolver/MatrixIter.cpp:635-819) with scaler_cgstab.
-  void solve(const mmx_param_iter& p, double* d_xout, int& nitr, int initial_guess) {
-    check_params(p);
+  // scal(n, ia, ja, a, b, a_scal, 0) on the device copies (ILU_class.cpp:904-954).  The first pass
+  // over a set of values (since set_values) rewrites them, so a factor of the unscaled values is
+  // dropped; a repeated pass multiplies by 1 (or 1 + 2^-52 where diag * (1 / diag) rounds below 1)
+  // and keeps the factor (valVersion stays)
+  void scale_rows() {
+    if (!allDiag) throw Error(MMADMM_ERR_INVALID, "ParamIter.iscal = 1 needs a diagonal entry in every row");
+    if (!d_ascal.p) d_ascal.alloc(n);
+    launch_scale_rows(nblk, d_desc.p, d_ia.p, d_adiag.p, d_a.p, d_b.p, d_ascal.p, st);
+    MMX_HIP(hipGetLastError());
+    scaled = true;
+    if (scaledVersion != valVersion) {
+      scaledVersion = valVersion;
+      factVersion = -1;
+    }
+  }
+
+  // the stored directions of ORTHOMIN(north): allocated on the first such solve, again when north changes
+  void omin_buffers(int north) {
+    if (ominNorth == north) return;
+    ominNorth = 0;
+    try {
+      d_oq.alloc((size_t)north * n);
+      d_oaq.alloc((size_t)north * n);
+      d_oms.alloc(2 * (size_t)north);
+      d_opart.alloc((size_t)std::max(north, 2) * vec_grid(n));
+    } catch (...) {
+      (void)hipGetLastError();  // (the failed allocation's error is reported by the exception)
+      d_oq.alloc(0);
+      d_oaq.alloc(0);
+      throw;
+    }
+    ominNorth = north;
+  }
+
+  // the iterations of scaler_orthomin (iaccel 1, accel_class.cpp:12-191) and scaler_conj (iaccel -1,
+  // accel_class.cpp:193-228, 402-491) after the initial residual; the host polls conv once per
+  // iteration, as the CG-STAB loop does
+  void accel_iterate(const mmx_param_iter& p, double* d_xout, int initial_guess, int& conv, int& it) {
+    const bool omin = p.iaccel == 1;
+    const int gv = vec_grid(n);
+    // x = 0, res = b or res = b - A x; the CG direction q (d_p) and aq (d_avbar) start at 0
+    if (initial_guess == 0) {
+      launch_cgs_init(0, n, d_b.p, d_xout, d_res.p, d_res0.p, d_p.p, d_avbar.p, 0, d_part.p, st);
+    } else {
+      spmv(0, d_xout, d_res.p, nullptr);
+      launch_cgs_init(1, n, d_b.p, d_xout, d_res.p, d_res0.p, d_p.p, d_avbar.p, 0, d_part.p, st);
+    }
+    const double ctol = p.resid_reduc;
+    MMX_HIP(hipMemcpyAsync(&d_asc.p->ctol, &ctol, sizeof(double), hipMemcpyHostToDevice, st));
+    launch_acc_fin(0, d_part.p, gv, 0, d_asc.p, st);
+    const double* tol = tolSet ? d_tol.p : nullptr;
+    double* vk = d_vbar.p;   // (LU)^-1 res
+    double* avk = d_t.p;     // A vk
+    int k = 0;               // ORTHOMIN's iter_count
+    for (int iter = 1; iter <= p.nitmax; ++iter) {
+      ++it;
+      MMX_HIP(hipMemsetAsync(tickets(), 0, 8 * sizeof(unsigned), st));
+      ilu_apply(0, d_res.p, nullptr, vk, tickets());
+      spmv(0, vk, avk, nullptr);
+      if (omin) {
+        launch_omin_dots(n, k, p.north, avk, d_oaq.p, d_oms.p, d_opart.p, st);
+        launch_omin_orth(n, k, p.north, vk, avk, d_res.p, d_oq.p, d_oaq.p, d_oms.p, d_asc.p, d_opart.p, st);
+        launch_omin_update(n, d_oq.p + (size_t)k * n, d_oaq.p + (size_t)k * n, vk, tol, d_xout, d_res.p, d_asc.p,
+                           d_opart.p, st);
+        if (++k > p.north - 1) k = 0;  // restart
+      } else {
+        launch_dot_into(n, d_res.p, vk, d_part.p, st);            // (res, v)
+        launch_acc_fin(1, d_part.p, gv, iter == 1, d_asc.p, st);  // rvk, aconj
+        launch_cg_dir(n, iter == 1, vk, avk, d_p.p, d_avbar.p, d_asc.p, d_part.p, st);
+        launch_cg_update(n, d_p.p, d_avbar.p, vk, tol, d_xout, d_res.p, d_asc.p, d_part.p, st);
+      }
+      MMX_HIP(hipGetLastError());
+      MMX_HIP(hipMemcpyAsync(h_asc, d_asc.p, sizeof(AccelScalars), hipMemcpyDeviceToHost, st));
+      spin_sync();
+      stats.iterations++;
+      if (h_asc->conv) {
+        conv = 1;
+        break;
+      }
+    }
+    if (p.nitmax <= 0) {  // the reference's loop body never runs; report non-convergence
+      MMX_HIP(hipMemcpyAsync(h_asc, d_asc.p, sizeof(AccelScalars), hipMemcpyDeviceToHost, st));
+      MMX_HIP(hipStreamSynchronize(st));
+    }
+  }
+
+  // MatrixIter::solve (lib/LASolver/MatrixIter.cpp:635-819) with scaler_cgstab, scaler_orthomin or
+  // scaler_conj.
+  void solve(const mmx_param_iter& pin, double* d_xout, int& nitr, int initial_guess) {
+    check_params(pin);
+    mmx_param_iter p = pin;
+    if (p.iaccel == -1) p.iscal = 0;  // no scaling for conjugate gradients (MatrixIter.cpp:661-665)
     if (!symbolic) throw Error(MMADMM_ERR_INVALID, "error: solve called with no symbolic ILU");
     if (p.level != level) throw Error(MMADMM_ERR_INVALID, "ParamIter.level differs from the one given to sfac");
     hipEvent_t t0 = nullptr;
@@ -868,7 +991,19 @@ struct SparseMatrix {
       tm[3].init();
       MMX_HIP(hipEventRecord(tm[3].a, st));
     }
+    if (p.iaccel == 1) omin_buffers(p.north);  // (may fail: before anything on the device changes)
+    if (p.iscal != 0)
+      scale_rows();
+    else
+      scaled = false;
     factor(false);
+    if (p.iaccel != 0) {
+      int conv = 0, it = 0;
+      accel_iterate(p, d_xout, initial_guess, conv, it);
+      finish_solve(conv, it, nitr, h_asc->rms, h_asc->rmsi);
+      (void)t0;
+      return;
+    }
     const int gv = vec_grid(n);
     if (initial_guess == 0) {
       launch_cgs_init(0, n, d_b.p, d_xout, d_res.p, d_res0.p, d_p.p, d_avbar.p, p.new_rhat == 0, d_part.p, st);
@@ -925,11 +1060,16 @@ struct SparseMatrix {
       MMX_HIP(hipMemcpyAsync(h_sc, d_sc.p, sizeof(CgsScalars), hipMemcpyDeviceToHost, st));
       MMX_HIP(hipStreamSynchronize(st));
     }
+    finish_solve(conv, it, nitr, h_sc->rms, h_sc->rmsi);
+    (void)t0;
+  }
+
+  void finish_solve(int conv, int it, int& nitr, double rms, double rmsi) {
     check_err();
     nitr = conv ? it : -1;
     stats.solves++;
-    stats.last_rms = h_sc->rms;
-    stats.rmsi = h_sc->rmsi;
+    stats.last_rms = rms;
+    stats.rmsi = rmsi;
     if (timing) {
       MMX_HIP(hipEventRecord(tm[3].b, st));
       MMX_HIP(hipEventSynchronize(tm[3].b));
@@ -937,7 +1077,6 @@ struct SparseMatrix {
       MMX_HIP(hipEventElapsedTime(&ms, tm[3].a, tm[3].b));
       stats.t_solve_ms += ms;
     }
-    (void)t0;
   }
 };
 
@@ -1313,6 +1452,19 @@ int mmx_matrix_get_factor(mmx_matrix m, int32_t* iaf, int32_t* jaf, double* af, 
       MMX_HIP(hipMemcpyAsync(af, M.d_af.p, sizeof(double) * M.jaf.size(), hipMemcpyDeviceToHost, M.st));
       MMX_HIP(hipStreamSynchronize(M.st));
     }
+  });
+}
+
+int mmx_matrix_get_scale(mmx_matrix m, double* scal) {
+  return guarded([&] {
+    MMX_M(m);
+    if (!scal) throw Error(MMADMM_ERR_INVALID, "bad arguments");
+    if (!M.scaled) {  // the reference sets a_scal = 1 when it does not scale (MatrixIter.cpp:675-680)
+      std::fill(scal, scal + M.n, 1.0);
+      return;
+    }
+    MMX_HIP(hipMemcpyAsync(scal, M.d_ascal.p, sizeof(double) * M.n, hipMemcpyDeviceToHost, M.st));
+    MMX_HIP(hipStreamSynchronize(M.st));
   });
 }
 

@@ -1,6 +1,7 @@
 // sparse_kernels.h -- launch interface of the LASolver HIP kernels (gfx950): CSR SpMV
-// (matmult), sync-free ILU(0) factor and triangular sweeps (scaler_ILU::factor / solve) and the
-// CG-STAB vector algebra (scaler_cgstab::acc_scaler).  See DESIGN.md §LASolver.
+// (matmult), sync-free ILU(0) factor and triangular sweeps (scaler_ILU::factor / solve), the
+// CG-STAB vector algebra (scaler_cgstab::acc_scaler) and, in accel_kernels.hip, ORTHOMIN, CG and the
+// row scaling (scaler_orthomin, scaler_conj, scal).  See DESIGN.md §LASolver.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -164,6 +165,42 @@ void launch_cgs_update(int n, const double* vbar, const double* z, const double*
                        double* partials, hipStream_t st);
 // Scalar finalisers (one workgroup).  mode 0 init, 1 alpha, 2 omega, 3 update.
 void launch_cgs_fin(int mode, const double* partials, int nblk, CgsScalars* sc, hipStream_t st);
+
+// ---- accel_kernels.hip: row scaling, ORTHOMIN and CG (scal, scaler_orthomin, scaler_conj) ----
+// Scalar state of the ORTHOMIN / CG accelerators on the device, and the per-iteration results the
+// host polls (CgsScalars stays CG-STAB's: the sweeps' prologues read it).
+struct AccelScalars {
+  double rmsi, rms, ctol, iconv;
+  double ohm;               // the step length of the iteration
+  double rvk, rvkm, aconj;  // CG: (res, v), its previous value, their ratio
+  int conv;
+  int pad;
+};
+// scal(..., scaltype 0) over the SpMV row blocks desc: per row f = 1 / (a[adiag[row]] + 1e-300);
+// every entry of the row and b[row] multiplied by f once; a_scal[row] = f.  Every row needs its
+// diagonal (adiag >= 0) and a block holds at most 4 * kSpmvBlock rows.
+void launch_scale_rows(int nblk, const int4* desc, const int* ia, const int* adiag, double* a, double* b,
+                       double* a_scal, hipStream_t st);
+// ORTHOMIN with k stored directions (q, Aq: north vectors of n; oms: AqAq[north], a_mult[north];
+// partials: max(k, 2) * vec_grid(n) doubles).  dots: a_mult[j] = -(Avk, Aq[j]) / (AqAq[j] + tiny),
+// j < k, Avk read once per group of 4 vectors.  orth: q[k] = vk + sum a_mult[j] q[j], Aq[k]
+// likewise, AqAq[k] and sc->ohm = (Aq[k], res) / (AqAq[k] + tiny) from the same pass.  update: sol
+// += ohm q[k], res -= ohm Aq[k], sc->rms / iconv / conv.
+void launch_omin_dots(int n, int k, int north, const double* avk, const double* Aq, double* oms, double* partials,
+                      hipStream_t st);
+void launch_omin_orth(int n, int k, int north, const double* vk, const double* avk, const double* res, double* q,
+                      double* Aq, double* oms, AccelScalars* sc, double* partials, hipStream_t st);
+void launch_omin_update(int n, const double* qk, const double* aqk, const double* vk, const double* toler, double* x,
+                        double* res, AccelScalars* sc, double* partials, hipStream_t st);
+// CG.  dir: q = v, aq = avk (first) or q = v + aconj q, aq = avk + aconj aq; sc->ohm = rvk / (q, aq),
+// rvkm = rvk.  update: x += ohm q, res -= ohm aq, sc->rms / iconv / conv.
+void launch_cg_dir(int n, int first, const double* v, const double* avk, double* q, double* aq, AccelScalars* sc,
+                   double* partials, hipStream_t st);
+void launch_cg_update(int n, const double* q, const double* aq, const double* v, const double* toler, double* x,
+                      double* res, AccelScalars* sc, double* partials, hipStream_t st);
+// Finalisers over [block][2] partials: mode 0 sc->rmsi from launch_cgs_init's slot 0 (conv = 0);
+// mode 1 sc->rvk from launch_dot_into's slot 1 and, unless first, aconj = rvk / rvkm.
+void launch_acc_fin(int mode, const double* partials, int nblk, int first, AccelScalars* sc, hipStream_t st);
 
 // Measurement utility: dst = src over n2 16-byte elements (streaming copy ceiling; variants in
 // sparse_kernels.hip).

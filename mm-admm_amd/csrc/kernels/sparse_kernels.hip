@@ -20,6 +20,7 @@
 
 #include <cstdlib>
 
+#include "block_reduce.h"  // block_sum: the fixed-shape block tree, shared with accel_kernels.hip
 #include "sparse_kernels.h"
 
 namespace mmx {
@@ -72,22 +73,6 @@ __device__ __forceinline__ int take_ticket(unsigned* ticket) {
   if (threadIdx.x == 0) s_blk = (int)atomicAdd(ticket, 1u);
   __syncthreads();
   return s_blk;
-}
-
-// fixed-shape block tree over NV values per thread; thread 0 returns the sums
-template <int NV, int B>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double (*red)[NV]) {
-#pragma unroll
-  for (int i = 0; i < NV; ++i) red[threadIdx.x][i] = v[i];
-  __syncthreads();
-  for (int w = B / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w)
-#pragma unroll
-      for (int i = 0; i < NV; ++i) red[threadIdx.x][i] = red[threadIdx.x][i] + red[threadIdx.x + w][i];
-    __syncthreads();
-  }
-#pragma unroll
-  for (int i = 0; i < NV; ++i) v[i] = red[0][i];
 }
 
 }  // namespace

@@ -7,7 +7,11 @@ the MI355X kernels of libmmadmm.so (include/mmx_sparse.h).
   MatrixIter(struc) / MatrixIter(n, ia, ja)
                                 aValue / bValue as numpy views (a, b), set_toler, sfac(param),
                                 solve(param, x, initial_guess) -> nitr (x updated in place),
-                                matmult(x) (the module-level matmult of accel_class.cpp)
+                                matmult(x) (the module-level matmult of accel_class.cpp),
+                                get_scale() (a_scal of the last solve)
+ParamIter.iaccel selects CG-STAB (0), ORTHOMIN(north) (1) or conjugate gradients (-1); iscal = 1 scales
+the rows by their diagonal on the device (the host arrays a / b keep the unscaled values, and every
+solve() uploads them again).  RCM ordering, drop-tolerance ILU and pivoting raise MMADMMError.
 There is no CPU fallback: every call runs on the GPU through the C-ABI.
 """
 import ctypes
@@ -87,6 +91,7 @@ def lib():
     L.mmx_matrix_ilu_solve_device.argtypes = [vp, vp, vp]
     L.mmx_matrix_factor_nnz.argtypes = [vp, ctypes.POINTER(ll)]
     L.mmx_matrix_get_factor.argtypes = [vp, c_int_p, c_int_p, c_double_p, c_int_p]
+    L.mmx_matrix_get_scale.argtypes = [vp, c_double_p]
     L.mmx_matrix_set_timing.argtypes = [vp, i]
     L.mmx_matrix_stats_get.argtypes = [vp, ctypes.POINTER(SparseStats)]
     L.mmx_matrix_stats_reset.argtypes = [vp]
@@ -199,11 +204,19 @@ class MatrixIter:
         """Returns nitr (-1 if not converged); x (float64 array of n) receives the solution."""
         if x.dtype != np.float64 or not x.flags.c_contiguous or len(x) != self.n:
             raise ValueError("x must be a contiguous float64 array of length n")
+        if param.iaccel == -1:  # no scaling for conjugate gradients (MatrixIter.cpp:661-665)
+            param.iscal = 0
         self.upload()
         nitr = ctypes.c_int()
         _check(lib().mmx_matrix_solve(self.h, ctypes.byref(param), x.ctypes.data_as(c_double_p),
                                       ctypes.byref(nitr), int(initial_guess)))
         return nitr.value
+
+    def get_scale(self):
+        """a_scal of the last solve: 1 / (diagonal + 1e-300) after iscal = 1, else all 1.0."""
+        f = np.zeros(self.n)
+        _check(lib().mmx_matrix_get_scale(self.h, f.ctypes.data_as(c_double_p)))
+        return f
 
     def matmult(self, x):
         _check(lib().mmx_matrix_set_values(self.h, _f64(self.a).ctypes.data_as(c_double_p)))
@@ -244,6 +257,8 @@ class MatrixIter:
         _check(lib().mmx_matrix_matmult_device(self.h, ctypes.c_void_p(xptr), ctypes.c_void_p(yptr)))
 
     def solve_device(self, param, xptr, initial_guess=0):
+        if param.iaccel == -1:
+            param.iscal = 0
         nitr = ctypes.c_int()
         _check(lib().mmx_matrix_solve_device(self.h, ctypes.byref(param), ctypes.c_void_p(xptr),
                                              ctypes.byref(nitr), int(initial_guess)))
