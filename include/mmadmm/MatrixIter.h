@@ -21,14 +21,21 @@
 //   set_toler(const double*)                      MatrixIter.cpp:443-453  -> mmx_matrix_set_toler
 //   solve(ParamIter&, double* x, int& nitr, ig)   MatrixIter.cpp:635-819  -> mmx_matrix_set_values,
 //                                                                            mmx_matrix_set_rhs, mmx_matrix_solve
+//   set_user_ordering_vector(int* lorder)         MatrixIter.cpp:566-610  -> mmx_matrix_set_ordering
+//   rcm(ia, ja, n, lorder)                        rcm.cpp:34-161          -> mmx_rcm (host)
 //
 // The matrix values and the right-hand side live in host arrays, as in the reference: aValue(k) and
 // bValue(i) return references into them, and solve() hands both to the device (the values are
 // factored again, as the reference re-factors in every solve, MatrixIter.cpp:684).  Non-convergence
 // is nitr = -1, as in the reference.  Errors the reference throws as General_Exception (a bad entry,
 // a packed structure) are thrown as General_Exception here too; so are the C-ABI's other failures
-// (no GPU, an unsupported ParamIter setting: RCM ordering, drop-tolerance ILU and pivoting are not
-// implemented).  ParamIter.iaccel selects CG-STAB (0), ORTHOMIN(north) (1) or conjugate gradients (-1);
+// (no GPU, an unsupported ParamIter setting: drop-tolerance ILU and pivoting are not implemented).
+// Ordering: set_user_ordering_vector(lorder) before sfac orders the ILU by any permutation
+// (lorder[new] = old) and, as in the reference, overrides ParamIter.order; rcm() computes the
+// reference's RCM ordering, so set_user_ordering_vector of it is the reference's order = 1.
+// ParamIter.order = 1 on a matrix with no user ordering is still refused (the library does not
+// compute the ordering behind the caller's back yet): a default-constructed ParamIter needs either
+// the user ordering or order = 0.  ParamIter.iaccel selects CG-STAB (0), ORTHOMIN(north) (1) or conjugate gradients (-1);
 // iscal = 1 scales the rows by their diagonal on the device.  As the reference, solve() with
 // iaccel = -1 sets param.iscal = 0.  One visible difference: the reference's scal() rewrites a and b
 // in place, here only the device copies are scaled -- aValue() / bValue() after a scaled solve still
@@ -203,7 +210,12 @@ public:
         detail::check(mmx_matrix_create(mmx_device(), n_in, ia.data(), ja.data(), &m_));
     }
 
-    // symbolic level-of-fill ILU (natural order)
+    // user ordering vector lorder[new_order] = old_order (n entries, copied; the column ordering is
+    // the row ordering): overrides ParamIter.order from the next sfac on.  A null pointer changes
+    // nothing; an out-of-range or repeated index throws (the reference's error_3 / error_4).
+    void set_user_ordering_vector(int* lorder_in) { detail::check(mmx_matrix_set_ordering(m_, lorder_in)); }
+
+    // symbolic level-of-fill ILU (natural order, or the user ordering when one is set)
     void sfac(ParamIter& param) {
         const mmx_param_iter p = param.abi();
         detail::check(mmx_matrix_sfac(m_, &p));
@@ -277,6 +289,9 @@ private:
     std::vector<double> a, b;
     mmx_matrix m_ = nullptr;
 };
+
+// the reference's RCM ordering of the pattern (rcm.cpp): lorder[new_order] = old_order, on the host
+inline void rcm(const int ia[], const int ja[], int n, int lorder[]) { detail::check(mmx_rcm(n, ia, ja, lorder)); }
 
 }  // namespace SparseItObj
 

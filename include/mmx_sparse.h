@@ -25,12 +25,30 @@
  *   mmx_matrix_get_factor          rowsp[i].af (read back)         lib/LASolver/ILU_class.h:24-90
  *   mmx_matrix_get_scale           a_scal (read back)              lib/LASolver/MatrixIter.cpp:667-680
  *   mmx_ilu_symbolic               scaler_ILU::sfac2 / merge2      lib/LASolver/ILU_class.cpp:17-295
+ *   mmx_matrix_set_ordering        set_user_ordering_vector        lib/LASolver/MatrixIter.cpp:566-610
+ *   mmx_matrix_clear_ordering      (none: back to natural order)
+ *   mmx_matrix_get_ordering        get_lorder                      lib/LASolver/MatrixIter.cpp:491-518
+ *   mmx_rcm                        rcm                             lib/LASolver/rcm.cpp
  *
- * Supported ParamIter settings: natural order (order 0), level-of-fill ILU (drop_ilu 0) at any
- * level, no pivoting (ipiv 0); no scaling or diagonal row scaling (iscal 0 / 1); CG-STAB with either
- * rhat (iaccel 0), ORTHOMIN(north) (iaccel 1, north >= 1) or conjugate gradients (iaccel -1, which
- * forces iscal 0 as the reference does).  RCM ordering, drop-tolerance ILU and pivoting return
- * MMADMM_ERR_INVALID with a message.
+ * Supported ParamIter settings: level-of-fill ILU (drop_ilu 0) at any level, no pivoting (ipiv 0);
+ * no scaling or diagonal row scaling (iscal 0 / 1); CG-STAB with either rhat (iaccel 0),
+ * ORTHOMIN(north) (iaccel 1, north >= 1) or conjugate gradients (iaccel -1, which forces iscal 0 as
+ * the reference does).  Drop-tolerance ILU and pivoting return MMADMM_ERR_INVALID with a message.
+ *
+ * Ordering.  The ILU is built in natural order (order 0) or in a user ordering vector
+ * (mmx_matrix_set_ordering: lorder[new] = old, any permutation; the column ordering equals the row
+ * ordering).  As in the reference a user ordering overrides ParamIter.order, which is then ignored, so
+ * mmx_matrix_set_ordering(m, the vector of mmx_rcm) gives exactly what order = 1 gives there.
+ * ParamIter.order = 1 on a matrix WITHOUT a user ordering is still MMADMM_ERR_INVALID: the library
+ * does not compute an ordering the caller did not ask for by vector (accepting it is a one-line
+ * follow-up; existing callers rely on the refusal).  A default-constructed ParamIter (order 1)
+ * therefore needs either the vector or order = 0.
+ * With an ordering in effect (from the mmx_matrix_sfac after it was set) the symbolic and numeric
+ * factor are those of B = P A P^T with sorted rows -- mmx_matrix_factor_nnz / mmx_matrix_get_factor
+ * return them in the new numbering, as the reference's rowsp -- and mmx_matrix_ilu_solve applies
+ * P^T (LU)^-1 P.  Only the preconditioner is permuted: SpMV, dot products, row scaling, toler, x and b
+ * stay in the caller's numbering.  A separate column ordering (set_user_ordering_vector_column) is
+ * not supported.
  *
  * Row scaling (iscal 1; scal(), lib/LASolver/ILU_class.cpp:904-954) acts on the matrix's device
  * copies at the start of every such solve: row i and b[i] are multiplied by f = 1 / (a_ii + 1e-300).
@@ -64,7 +82,7 @@ extern "C" {
 #endif
 
 typedef struct mmx_param_iter {
-  int order;          /* 0 natural (1 RCM: not supported) */
+  int order;          /* 0 natural (1 RCM: refused; ignored once mmx_matrix_set_ordering has set a vector) */
   int level;          /* level of fill of the ILU */
   int drop_ilu;       /* 0 level-of-fill ILU (1 drop tolerance: not supported) */
   int ipiv;           /* 0 no pivoting */
@@ -117,6 +135,15 @@ int mmx_matrix_set_rhs(mmx_matrix m, const double* b);
 int mmx_matrix_set_rhs_device(mmx_matrix m, const double* d_b);
 int mmx_matrix_set_toler(mmx_matrix m, const double* tol);
 int mmx_matrix_sfac(mmx_matrix m, const mmx_param_iter* p);
+/* User ordering vector for the ILU: lorder[new] = old (n entries, copied); the column ordering equals
+ * the row ordering.  Null: no-op.  An out-of-range or repeated index: MMADMM_ERR_INVALID (the
+ * reference's error_3 / error_4).  In effect from the next mmx_matrix_sfac on, and then
+ * ParamIter.order is ignored; until then the structure of the last sfac stays in use. */
+int mmx_matrix_set_ordering(mmx_matrix m, const int32_t* lorder);
+/* back to natural order at the next mmx_matrix_sfac (no reference counterpart) */
+int mmx_matrix_clear_ordering(mmx_matrix m);
+/* the ordering the current symbolic factor was built with (n entries; the identity when none was set) */
+int mmx_matrix_get_ordering(mmx_matrix m, int32_t* lorder);
 /* x: initial guess on entry when initial_guess != 0; solution on exit */
 int mmx_matrix_solve(mmx_matrix m, const mmx_param_iter* p, double* x, int* nitr, int initial_guess);
 int mmx_matrix_solve_device(mmx_matrix m, const mmx_param_iter* p, double* d_x, int* nitr, int initial_guess);
@@ -141,6 +168,13 @@ int mmx_matrix_destroy(mmx_matrix m);
  * and diag (n, row-relative). */
 int mmx_ilu_symbolic(int n, const int32_t* ia, const int32_t* ja, int level, long long* nnzf, int32_t* iaf,
                      int32_t* jaf, int32_t* diag);
+
+/* Host-only reverse Cuthill-McKee ordering of the pattern (rcm(), lib/LASolver/rcm.cpp), element for
+ * element: lorder[new] = old (n entries).  The pattern is symmetrised first and need not hold its
+ * diagonal.  A disconnected ("reducible") graph, or a row j holding column i twice for an entry
+ * (i, j), returns MMADMM_ERR_INVALID with a message.  mmx_matrix_set_ordering(m, lorder) with this
+ * vector gives what ParamIter.order = 1 gives in the reference. */
+int mmx_rcm(int n, const int32_t* ia, const int32_t* ja, int32_t* lorder);
 
 /* Diagnostics (host only): the chain/band schedule the sweeps would use for the ILU(level) of this
  * pattern.  info[16]: ok, E, R, RI, bands, chains, max chain length,

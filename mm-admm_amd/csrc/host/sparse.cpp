@@ -1,7 +1,9 @@
 // sparse.cpp -- host side of the LASolver replacement (include/mmx_sparse.h): MatrixStruc
-// packing, the symbolic ILU (level of fill, natural order) and the device-resident MatrixIter
-// whose numeric factor, sweeps, SpMV and CG-STAB run as HIP kernels (kernels/sparse_kernels.hip), as
-// do ORTHOMIN, CG and the row scaling (kernels/accel_kernels.hip).
+// packing, the symbolic ILU (level of fill; natural order or a user ordering vector, for which it
+// runs on B = P A P^T) and the device-resident MatrixIter whose numeric factor, sweeps, SpMV and
+// CG-STAB run as HIP kernels (kernels/sparse_kernels.hip), as do ORTHOMIN, CG and the row scaling
+// (kernels/accel_kernels.hip) and the ordering's permutation passes (kernels/order_kernels.hip).
+// The RCM ordering itself is host code (rcm.cpp).
 #include <omp.h>
 
 #include <algorithm>
@@ -20,6 +22,7 @@
 #include "../kernels/sparse_kernels.h"
 #include "chain_sched.h"
 #include "common.h"
+#include "rcm.h"
 
 namespace mmx {
 namespace {
@@ -205,8 +208,10 @@ int spmv_version() {
   return v;
 }
 
-void check_params(const mmx_param_iter& p) {
-  if (p.order != 0) throw Error(MMADMM_ERR_INVALID, "unsupported ParamIter.order (only natural ordering, 0)");
+// userOrder: a user ordering vector is set, which overrides ParamIter.order (get_lorder,
+// lib/LASolver/MatrixIter.cpp:491-518)
+void check_params(const mmx_param_iter& p, bool userOrder = false) {
+  if (p.order != 0 && !userOrder) throw Error(MMADMM_ERR_INVALID, "unsupported ParamIter.order (only natural ordering, 0)");
   if (p.drop_ilu != 0) throw Error(MMADMM_ERR_INVALID, "unsupported ParamIter.drop_ilu (only level-of-fill ILU, 0)");
   if (p.ipiv != 0) throw Error(MMADMM_ERR_INVALID, "unsupported ParamIter.ipiv (only no pivoting, 0)");
   if (p.iscal != 0 && p.iscal != 1)
@@ -307,6 +312,15 @@ struct SparseMatrix {
   int ominNorth = 0;
   DevBuf<AccelScalars> d_asc;
   AccelScalars* h_asc = nullptr;
+  // user ordering vector (set_user_ordering_vector, MatrixIter.cpp:566-610): lorderUser[new] = old,
+  // in effect from the next sfac on.  ordered: the symbolic factor in use was built on
+  // B = P A P^T (rows sorted); lorder is its ordering, d_aB = a[bsrc] the values of B the factor
+  // kernels read, d_pv the sweeps' operand / result in the new numbering.  None of these buffers
+  // exists in natural order.
+  std::vector<int> lorderUser, lorder;
+  bool haveUser = false, ordered = false;
+  DevBuf<int> d_iaB, d_jaB, d_bsrc, d_lord, d_inv;
+  DevBuf<double> d_aB, d_pv;
   bool timing = false;
   mmx_sparse_stats stats{};
   Timer tm[4];  // spmv, sweeps, factor, whole solve
@@ -423,12 +437,41 @@ struct SparseMatrix {
   unsigned* errw() { return d_ctl.p + 8; }
 
   void sfac(const mmx_param_iter& p) {
-    check_params(p);
+    check_params(p, haveUser);
     PhaseTimer pt("sfac");
-    symbolic_ilu(n, ia, ja, p.level, iaf, jaf, dgRel);
+    // with a user ordering: B = P A P^T with sorted rows and the gather map of its values; from here
+    // on everything is built on (pia, pja) -- B's pattern, or A's own in natural order
+    const bool ord = haveUser;
+    std::vector<int> iaB, jaB, bsrc;
+    if (ord) {
+      permuted_pattern(iaB, jaB, bsrc);
+      pt.mark("permuted pattern");
+    }
+    const std::vector<int>& pia = ord ? iaB : ia;
+    const std::vector<int>& pja = ord ? jaB : ja;
+    symbolic_ilu(n, pia, pja, p.level, iaf, jaf, dgRel);
     pt.mark("symbolic");
     level = p.level;
-    std::vector<int> dg(n), amap(nnz);
+    ordered = ord;
+    if (ord) {  // (on the caller's thread: the helpers below do not set the device)
+      lorder = lorderUser;
+      std::vector<int> inv(n);
+      for (int i = 0; i < n; ++i) inv[lorder[i]] = i;
+      d_lord.upload(lorder.data(), lorder.size(), st);
+      d_inv.upload(inv.data(), inv.size(), st);
+      d_iaB.upload(iaB.data(), iaB.size(), st);
+      d_jaB.upload(jaB.data(), std::max<size_t>(jaB.size(), 1), st);
+      d_bsrc.upload(bsrc.data(), std::max<size_t>(bsrc.size(), 1), st);
+      d_aB.alloc(std::max<size_t>(jaB.size(), 1));
+      d_pv.alloc(n);
+      MMX_HIP(hipStreamSynchronize(st));  // (inv goes out of scope)
+    } else if (d_lord.p) {  // back to natural order: the ordered factor's buffers go
+      lorder.clear();
+      for (DevBuf<int>* b : {&d_iaB, &d_jaB, &d_bsrc, &d_lord, &d_inv}) b->alloc(0);
+      d_aB.alloc(0);
+      d_pv.alloc(0);
+    }
+    std::vector<int> dg(n), amap(pja.size());
     for (int i = 0; i < n; ++i) dg[i] = iaf[i] + dgRel[i];
     // the sweep and factor schedules (the bulk of the host set-up: DESIGN.md §7b) depend only on the
     // factor's pattern: built on helper threads while this one prepares the rest
@@ -489,7 +532,7 @@ struct SparseMatrix {
     for (int i = 0; i < n; ++i) {
       const int* b = jaf.data() + iaf[i];
       const int* e = jaf.data() + iaf[i + 1];
-      for (int k = ia[i]; k < ia[i + 1]; ++k) amap[k] = (int)(std::lower_bound(b, e, ja[k]) - jaf.data());
+      for (int k = pia[i]; k < pia[i + 1]; ++k) amap[k] = (int)(std::lower_bound(b, e, pja[k]) - jaf.data());
     }
     d_iaf.upload(iaf.data(), iaf.size(), st);
     d_jaf.upload(jaf.data(), jaf.size(), st);
@@ -574,6 +617,9 @@ struct SparseMatrix {
         if (e) std::rethrow_exception(e);
       pt.mark("chain + factor schedules, sweep uploads (joined)");
       // (the sweeps address their granules through 32-bit byte offsets: rows < 2^27)
+      // (an ordered pattern keeps a valid chain schedule however long its modelled path: measured
+      // at n = 2 M with RCM, 435 k modelled iterations for 5,656 levels, the chain sweeps still took
+      // 12.3 ms against 17.1 ms for the level-scheduled ones; DESIGN.md LASolver, ordering)
       useChain = upF && upB && n < (1 << 27);
     }
     useChainFactor = false;
@@ -599,9 +645,9 @@ struct SparseMatrix {
         for (int i = 0; i < n; ++i) {
           int ok = (dg[i] - iaf[i] <= kFacWaveNL && iaf[i + 1] - dg[i] - 1 <= 64) ? 1 : 0;
           bool inc = true;
-          for (int k = ia[i] + 1; k < ia[i + 1] && inc; ++k) inc = amap[k] > amap[k - 1];
+          for (int k = pia[i] + 1; k < pia[i + 1] && inc; ++k) inc = amap[k] > amap[k - 1];
           if (ok && !inc) {
-            std::vector<int> v(amap.begin() + ia[i], amap.begin() + ia[i + 1]);
+            std::vector<int> v(amap.begin() + pia[i], amap.begin() + pia[i + 1]);
             std::sort(v.begin(), v.end());
             ok = std::adjacent_find(v.begin(), v.end()) == v.end() ? 1 : 0;
           }
@@ -636,6 +682,35 @@ struct SparseMatrix {
     pt.mark("factor set-up + uploads");
     release(FS);
     symbolic = true;
+  }
+
+  // B = P A P^T for lorderUser: row i of B is row lorder[i] of A with its columns mapped through
+  // invord and sorted ascending (scaler_ILU::sfac2 / factor, ILU_class.cpp:188-216, 369-418);
+  // bsrc[k] = the entry of A that B's k-th entry comes from
+  void permuted_pattern(std::vector<int>& iaB, std::vector<int>& jaB, std::vector<int>& bsrc) const {
+    const std::vector<int>& lo = lorderUser;
+    std::vector<int> inv(n);
+    for (int i = 0; i < n; ++i) inv[lo[i]] = i;
+    iaB.assign((size_t)n + 1, 0);
+    for (int i = 0; i < n; ++i) iaB[i + 1] = iaB[i] + (ia[lo[i] + 1] - ia[lo[i]]);
+    jaB.resize((size_t)nnz);
+    bsrc.resize((size_t)nnz);
+#pragma omp parallel
+    {
+      std::vector<std::pair<int, int>> row;
+#pragma omp for schedule(dynamic, 4096)
+      for (int i = 0; i < n; ++i) {
+        const int r = lo[i];
+        row.clear();
+        for (int k = ia[r]; k < ia[r + 1]; ++k) row.emplace_back(inv[ja[k]], k);
+        std::sort(row.begin(), row.end());
+        int o = iaB[i];
+        for (const auto& e : row) {
+          jaB[o] = e.first;
+          bsrc[o++] = e.second;
+        }
+      }
+    }
   }
 
   // the schedules' host images (GBs at C4) are freed where they are done with: the sweep schedules
@@ -808,19 +883,25 @@ struct SparseMatrix {
       fepoch = 1;
     }
     begin(2);
+    // the matrix the factor kernels read: A, or with an ordering B = P A P^T, its values gathered
+    // from A's here (the values changed, or this would not run)
+    const int* f_ia = ordered ? d_iaB.p : d_ia.p;
+    const int* f_ja = ordered ? d_jaB.p : d_ja.p;
+    const double* f_a = ordered ? d_aB.p : d_a.p;
+    if (ordered) launch_order_vals((long long)nnz, d_bsrc.p, d_a.p, d_aB.p, st);
     if (useChainFactor) {  // A into the factor pattern, the rows' values in schedule order, the factor
       MMX_HIP(hipMemsetAsync(chfac.af0.p, 0, chfac.af0.n * sizeof(double), st));
-      launch_scatter_a((long long)nnz, d_amap.p, d_a.p, chfac.af0.p, st);
+      launch_scatter_a((long long)nnz, d_amap.p, f_a, chfac.af0.p, st);
       launch_chain_fill((long long)chfac.vsrc.n, chfac.vsrc.p, chfac.af0.p, chfac.val.p, 0.0, st);
       launch_chain_factor(chfac.args, d_af.p, chfac.gU.p, fepoch, tickets(), errw(), st);
     } else if (facWave) {
-      launch_ilu_factor_wave(d_ia.p, d_a.p, d_amap.p, d_iaf.p, d_dg.p, d_piv.p, d_jaf.p, d_toff.p, d_tgt.p, d_permw.p, n,
+      launch_ilu_factor_wave(f_ia, f_a, d_amap.p, d_iaf.p, d_dg.p, d_piv.p, d_jaf.p, d_toff.p, d_tgt.p, d_permw.p, n,
                              d_af.p, d_flags.p, d_gF.n ? d_gF.p : nullptr, fepoch, tickets(), errw(), st);
     } else if (facLds)
-      launch_ilu_factor_lds(d_ia.p, d_a.p, d_amap.p, d_iaf.p, d_jaf.p, d_dg.p, d_piv.p, d_toff.p, d_tgt.p, d_permf.p, nchf,
+      launch_ilu_factor_lds(f_ia, f_a, d_amap.p, d_iaf.p, d_jaf.p, d_dg.p, d_piv.p, d_toff.p, d_tgt.p, d_permf.p, nchf,
                             d_af.p, d_flags.p, fepoch, tickets(), errw(), st);
     else
-      launch_ilu_factor(d_ia.p, d_ja.p, d_a.p, d_amap.p, d_iaf.p, d_jaf.p, d_dg.p, d_piv.p, d_permf.p, nchf, d_af.p,
+      launch_ilu_factor(f_ia, f_ja, f_a, d_amap.p, d_iaf.p, d_jaf.p, d_dg.p, d_piv.p, d_permf.p, nchf, d_af.p,
                         d_flags.p, fepoch, tickets(), errw(), st);
     if (useChain) {  // the sweeps read the factor's entries in schedule order
       launch_chain_fill(chf.nent, chf.src.p, d_af.p, chf.val.p, 0.0, st);
@@ -846,8 +927,18 @@ struct SparseMatrix {
   }
 
   // scaler_ILU::solve: out = (LU)^-1 src, or with the CG-STAB prologues (pro 1: p, pro 2: s)
+  // With an ordering: x = P^T (LU)^-1 P src (ILU_class.cpp:485-521) -- the operand gathered into the
+  // new numbering first, the result written back through the ordering by the pass that takes it from
+  // the backward sweep's granules (chain sweeps) or by a pass after the sweep (level sweeps).
   void ilu_apply(int pro, const double* src, double* p, double* out, unsigned* tk) {
     begin(1);
+    double* const userOut = out;
+    if (ordered) {
+      if (pro != 0) throw Error(MMADMM_ERR_INVALID, "fused CG-STAB prologues index rows naturally: not with an ordering");
+      launch_order_enter(n, d_lord.p, src, d_pv.p, st);
+      src = d_pv.p;
+      out = d_pv.p;  // (a sweep that stores its result: the forward sweep has read d_pv by then)
+    }
     const unsigned ey = next_epoch();
     if (useChain)
       launch_chain_sweep(true, pro, chf.E, chf.args, src, p, d_res.p, d_avbar.p, d_sc.p, nullptr, d_gy.p, nullptr, ey,
@@ -864,10 +955,14 @@ struct SparseMatrix {
     if (useChain) {
       launch_chain_sweep(false, 0, chb.E, chb.args, nullptr, nullptr, nullptr, nullptr, nullptr, d_gy.p, d_gx.p,
                          fromGran ? nullptr : out, ex, tk + 1, errw(), st);
-      if (fromGran) launch_gran_extract(n, d_gx.p, out, st);
+      if (fromGran && ordered)
+        launch_order_exit_gran(n, d_inv.p, d_gx.p, userOut, st);
+      else if (fromGran)
+        launch_gran_extract(n, d_gx.p, out, st);
     } else
       launch_sweep(false, 0, d_iaf.p, d_jaf.p, d_dg.p, d_af.p, d_permb.p, nchb, nullptr, nullptr, nullptr, nullptr,
                    nullptr, d_gy.p, d_gx.p, out, ex, tk + 1, errw(), st);
+    if (ordered && !(useChain && fromGran)) launch_order_exit(n, d_inv.p, d_pv.p, userOut, st);
     MMX_HIP(hipGetLastError());
     const float ms = end(1);
     stats.sweeps += 2;
@@ -981,7 +1076,7 @@ struct SparseMatrix {
   // MatrixIter::solve (lib/LASolver/MatrixIter.cpp:635-819) with scaler_cgstab, scaler_orthomin or
   // scaler_conj.
   void solve(const mmx_param_iter& pin, double* d_xout, int& nitr, int initial_guess) {
-    check_params(pin);
+    check_params(pin, haveUser);
     mmx_param_iter p = pin;
     if (p.iaccel == -1) p.iscal = 0;  // no scaling for conjugate gradients (MatrixIter.cpp:661-665)
     if (!symbolic) throw Error(MMADMM_ERR_INVALID, "error: solve called with no symbolic ILU");
@@ -1024,7 +1119,8 @@ struct SparseMatrix {
     // sweeps read one operand and store nothing but their results (n = 2 M: average sweep 2.61 ->
     // 2.16-2.20 ms, solve 55.6 -> 48.5-49.0 ms; MMX_CGS_UNFUSE=0: fused into the forward sweeps)
     const char* uf = getenv("MMX_CGS_UNFUSE");
-    const bool unfuse = !(uf && atoi(uf) == 0);
+    // (with an ordering always: the fused prologues index the rows naturally)
+    const bool unfuse = ordered || !(uf && atoi(uf) == 0);
     int conv = 0, it = 0;
     for (int iter = 1; iter <= p.nitmax; ++iter) {
       ++it;
@@ -1360,6 +1456,56 @@ int mmx_matrix_sfac(mmx_matrix m, const mmx_param_iter* p) {
     MMX_M(m);
     if (!p) throw Error(MMADMM_ERR_INVALID, "null parameters");
     M.sfac(*p);
+  });
+}
+
+int mmx_matrix_set_ordering(mmx_matrix m, const int32_t* lorder) {
+  return guarded([&] {
+    MMX_M(m);
+    if (!lorder) return;  // as the reference: a null vector changes nothing
+    std::vector<char> seen(M.n, 0);
+    for (int i = 0; i < M.n; ++i) {
+      const int j = lorder[i];
+      if (j < 0 || j >= M.n)
+        throw Error(MMADMM_ERR_INVALID, "error_3 in user ordering: lorder[" + std::to_string(i) + "] = " +
+                                            std::to_string(j) + " is out of range");
+      if (seen[j])
+        throw Error(MMADMM_ERR_INVALID, "error_4 in user ordering: index " + std::to_string(j) + " appears twice");
+      seen[j] = 1;
+    }
+    M.lorderUser.assign(lorder, lorder + M.n);
+    M.haveUser = true;
+  });
+}
+
+int mmx_matrix_clear_ordering(mmx_matrix m) {
+  return guarded([&] {
+    MMX_M(m);
+    M.haveUser = false;
+    std::vector<int>().swap(M.lorderUser);
+  });
+}
+
+int mmx_matrix_get_ordering(mmx_matrix m, int32_t* lorder) {
+  return guarded([&] {
+    MMX_M(m);
+    if (!lorder) throw Error(MMADMM_ERR_INVALID, "bad arguments");
+    if (!M.symbolic) throw Error(MMADMM_ERR_INVALID, "no symbolic factor (call mmx_matrix_sfac)");
+    for (int i = 0; i < M.n; ++i) lorder[i] = M.ordered ? M.lorder[i] : i;
+  });
+}
+
+int mmx_rcm(int n, const int32_t* ia, const int32_t* ja, int32_t* lorder) {
+  return guarded([&] {
+    if (n <= 0 || !ia || !lorder || (!ja && ia[n] > 0)) throw Error(MMADMM_ERR_INVALID, "mmx_rcm: bad arguments");
+    if (ia[0] != 0) throw Error(MMADMM_ERR_INVALID, "ia[0] must be 0");
+    for (int i = 0; i < n; ++i)
+      if (ia[i + 1] < ia[i]) throw Error(MMADMM_ERR_INVALID, "ia must be non-decreasing");
+    for (int k = 0; k < ia[n]; ++k)
+      if (ja[k] < 0 || ja[k] >= n) throw Error(MMADMM_ERR_INVALID, "column index out of range");
+    std::vector<int> lo;
+    mmx::rcm_order(n, ia, ja, lo);
+    std::copy(lo.begin(), lo.end(), lorder);
   });
 }
 

@@ -202,6 +202,16 @@ void launch_cg_update(int n, const double* q, const double* aq, const double* v,
 // mode 1 sc->rvk from launch_dot_into's slot 1 and, unless first, aconj = rvk / rvkm.
 void launch_acc_fin(int mode, const double* partials, int nblk, int first, AccelScalars* sc, hipStream_t st);
 
+// ---- order_kernels.hip: the permutation passes of an ordered ILU (lorder[new] = old) ----
+// aB[k] = a[bsrc[k]]: the values of B = P A P^T from A's, once per numeric factor
+void launch_order_vals(long long nnz, const int* bsrc, const double* a, double* aB, hipStream_t st);
+// v[i] = src[lorder[i]] (ahead of the forward sweep)
+void launch_order_enter(int n, const int* lorder, const double* src, double* v, hipStream_t st);
+// out[j] = y[invord[j]] (after a sweep that stores its result); the same from the backward sweep's
+// granules g (launch_gran_extract with the exit folded in)
+void launch_order_exit(int n, const int* invord, const double* y, double* out, hipStream_t st);
+void launch_order_exit_gran(int n, const int* invord, const uint64_t* g, double* out, hipStream_t st);
+
 // Measurement utility: dst = src over n2 16-byte elements (streaming copy ceiling; variants in
 // sparse_kernels.hip).
 void launch_stream_copy(int variant, long long n2, const double* src, double* dst, hipStream_t st);

@@ -8,10 +8,14 @@ the MI355X kernels of libmmadmm.so (include/mmx_sparse.h).
                                 aValue / bValue as numpy views (a, b), set_toler, sfac(param),
                                 solve(param, x, initial_guess) -> nitr (x updated in place),
                                 matmult(x) (the module-level matmult of accel_class.cpp),
-                                get_scale() (a_scal of the last solve)
+                                get_scale() (a_scal of the last solve),
+                                set_user_ordering_vector(lorder), clear_ordering(), get_ordering()
+  rcm(ia, ja)                   rcm() of lib/LASolver/rcm.cpp (host)
 ParamIter.iaccel selects CG-STAB (0), ORTHOMIN(north) (1) or conjugate gradients (-1); iscal = 1 scales
 the rows by their diagonal on the device (the host arrays a / b keep the unscaled values, and every
-solve() uploads them again).  RCM ordering, drop-tolerance ILU and pivoting raise MMADMMError.
+solve() uploads them again).  Ordering comes through MatrixIter.set_user_ordering_vector (any
+permutation; rcm(ia, ja) computes the reference's RCM ordering); ParamIter.order = 1 without such a
+vector, drop-tolerance ILU and pivoting raise MMADMMError.
 There is no CPU fallback: every call runs on the GPU through the C-ABI.
 """
 import ctypes
@@ -100,6 +104,10 @@ def lib():
     L.mmx_occupy.argtypes = [i, i, ctypes.c_double]
     L.mmx_occupy_wait.argtypes = []
     L.mmx_ilu_symbolic.argtypes = [i, c_int_p, c_int_p, i, ctypes.POINTER(ll), c_int_p, c_int_p, c_int_p]
+    L.mmx_rcm.argtypes = [i, c_int_p, c_int_p, c_int_p]
+    L.mmx_matrix_set_ordering.argtypes = [vp, c_int_p]
+    L.mmx_matrix_clear_ordering.argtypes = [vp]
+    L.mmx_matrix_get_ordering.argtypes = [vp, c_int_p]
     _cfg = True
     return L
 
@@ -199,6 +207,26 @@ class MatrixIter:
 
     def sfac(self, param):
         _check(lib().mmx_matrix_sfac(self.h, ctypes.byref(param)))
+
+    def set_user_ordering_vector(self, lorder):
+        """lorder[new] = old (MatrixIter.cpp:566-610): the ordering of the ILU from the next sfac on,
+        overriding ParamIter.order; None changes nothing, as the reference's null pointer."""
+        if lorder is None:
+            return
+        lorder = _i32(lorder)
+        if lorder.shape != (self.n,):
+            raise ValueError("the ordering vector must hold n entries")
+        _check(lib().mmx_matrix_set_ordering(self.h, lorder.ctypes.data_as(c_int_p)))
+
+    def clear_ordering(self):
+        """Back to natural order at the next sfac."""
+        _check(lib().mmx_matrix_clear_ordering(self.h))
+
+    def get_ordering(self):
+        """The ordering the current symbolic factor was built with (the identity when none was set)."""
+        lorder = np.zeros(self.n, np.int32)
+        _check(lib().mmx_matrix_get_ordering(self.h, lorder.ctypes.data_as(c_int_p)))
+        return lorder
 
     def solve(self, param, x, initial_guess=0):
         """Returns nitr (-1 if not converged); x (float64 array of n) receives the solution."""
@@ -306,6 +334,17 @@ def ilu_symbolic(ia, ja, level):
     return iaf, jaf, dg
 
 
+def rcm(ia, ja):
+    """The reference's reverse Cuthill-McKee ordering (lib/LASolver/rcm.cpp) of the pattern, on the
+    host -> lorder with lorder[new] = old.  MatrixIter.set_user_ordering_vector(rcm(ia, ja)) is the
+    reference's ParamIter.order = 1."""
+    ia, ja = _i32(ia), _i32(ja)
+    n = len(ia) - 1
+    lorder = np.zeros(n, np.int32)
+    _check(lib().mmx_rcm(n, ia.ctypes.data_as(c_int_p), ja.ctypes.data_as(c_int_p), lorder.ctypes.data_as(c_int_p)))
+    return lorder
+
+
 def stream_copy_ms(src_ptr, dst_ptr, n, reps=20, device=0, variant=0):
     """Average ms of a 16-B-per-lane streaming copy of n doubles between two device buffers (the
     achievable HBM ceiling; 16 n bytes moved per copy)."""
@@ -320,7 +359,7 @@ def matmult(A, x):
     return A.matmult(x)
 
 
-__all__ = ["ParamIter", "MatrixStruc", "MatrixIter", "matmult", "ilu_symbolic", "stream_copy_ms", "MMADMMError"]
+__all__ = ["ParamIter", "MatrixStruc", "MatrixIter", "matmult", "ilu_symbolic", "rcm", "stream_copy_ms", "MMADMMError"]
 
 
 def occupy(blocks, ms, device=0):
