@@ -695,7 +695,7 @@ class Engine final : public EngineBase {
     streamWait();
   }
 
-  // host mirror of bidx<D> (admm_kernels.hip)
+  // host mirror of bidx<D> (admm_prox_common.h)
   static size_t bIndex(int s, int ij) {
     if (D == 3 && MMX_B3_PAIRS) return ((size_t)(s >> 6) * K * K + (ij & ~1)) * 64 + 2 * (s & 63) + (ij & 1);
     return ((size_t)(s >> 6) * K * K + ij) * 64 + (s & 63);
@@ -1653,7 +1653,7 @@ class Engine final : public EngineBase {
   size_t evUsed_ = 0;
   bool zFromX_ = false;
   bool fusePred_ = true;
-  static constexpr bool kZUInterleaved = (D == 2) && MMX_ZU_INTER;  // = kZUInter<D> (admm_kernels.hip)
+  static constexpr bool kZUInterleaved = (D == 2) && MMX_ZU_INTER;  // = kZUInter<D> (admm_common.h)
   double* uPtr() const { return kZUInterleaved ? z_.p + D : u_.p; }
   void clearU() {  // u = 0 (2D: the whole interleaved buffer, z included)
     if (kZUInterleaved)

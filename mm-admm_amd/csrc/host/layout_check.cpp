@@ -8,7 +8,11 @@
 #include "../kernels/layout.h"
 #include "common.h"
 
-extern "C" unsigned mmx_layout_admm(void);
+extern "C" unsigned mmx_layout_admm_prox(void);
+extern "C" unsigned mmx_layout_admm_prox_quad(void);
+extern "C" unsigned mmx_layout_admm_step(void);
+extern "C" unsigned mmx_layout_admm_euler(void);
+extern "C" unsigned mmx_layout_admm_util(void);
 extern "C" unsigned mmx_layout_sparse(void);
 extern "C" unsigned mmx_layout_chain(void);
 
@@ -18,7 +22,12 @@ void check_kernel_layout(unsigned hostWord) {
   const struct {
     const char* name;
     unsigned word;
-  } objs[] = {{"admm_kernels", mmx_layout_admm()}, {"sparse_kernels", mmx_layout_sparse()},
+  } objs[] = {{"admm_kernels_prox", mmx_layout_admm_prox()},
+              {"admm_kernels_prox_quad", mmx_layout_admm_prox_quad()},
+              {"admm_kernels_step", mmx_layout_admm_step()},
+              {"admm_kernels_euler", mmx_layout_admm_euler()},
+              {"admm_kernels_util", mmx_layout_admm_util()},
+              {"sparse_kernels", mmx_layout_sparse()},
               {"chain_sweep", mmx_layout_chain()}};
   for (const auto& o : objs)
     if (o.word != hostWord) {

@@ -19,7 +19,7 @@
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #define MMX_HD __host__ __device__ __forceinline__
-#define MMX_HD_COLD __host__ __device__ __attribute__((noinline))
+#define MMX_HD_COLD inline __host__ __device__ __attribute__((noinline))  // (inline: several objects include this)
 #else
 #define MMX_HD inline
 #define MMX_HD_COLD inline
@@ -303,6 +303,17 @@ MMX_HD_COLD double cr_resolve(double x, int num, int den, double h, int dir) {
   if (dir > 0) return vAboveM ? nb : h;
   return vAboveM ? h : nb;
 }
+#if defined(__HIP_DEVICE_COMPILE__)
+// The compiler sizes the register budget of cr_resolve and the xp:: helpers (the only non-inlined
+// device functions) from the launch bounds of the kernels that call them in the same object, and a
+// kernel's register count covers its callees.  This externally visible caller (never called) keeps
+// that budget at the default in every object, so a kernel's registers -- and its occupancy -- do
+// not depend on which other kernels share its object (measured: without it k_grad_simplex<2> goes
+// from 124 to 125 + 1 registers and from four waves per SIMD to three).
+__device__ __attribute__((used, noinline)) inline double cr_resolve_anchor(double x, double h) {
+  return cr_resolve(x, 3, 2, h, 1);
+}
+#endif
 
 // Round a normalised double-double (hi = RN(hi + lo)) that approximates x^(num/den) with
 // relative error < 2^-100; near a midpoint the exact decision (cr_resolve) is needed.

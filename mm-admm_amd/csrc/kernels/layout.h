@@ -1,13 +1,13 @@
 // layout.h -- the one place for every compile-time switch that changes the layout of a buffer
 // written by host code and read by a kernel (or the other way round).  Host and kernel
 // translation units include this header; each kernel object exports the layout word it was
-// compiled with (mmx_layout_admm / _sparse / _chain, extern "C"), and the host compares them with
+// compiled with (mmx_layout_admm_* / _sparse / _chain, extern "C"), and the host compares them with
 // its own before any HIP call (check_kernel_layout, host/layout_check.cpp): a library whose host and
 // kernel objects were built with different switches fails at create with MMADMM_ERR_INVALID
 // instead of computing on a misread buffer (round 5's z/u mismatch reached the GPU that way).
 #pragma once
 
-// 2D z / u: 1 = interleaved per vertex slot (admm_kernels.hip zu_*), 0 = two arrays (kept:
+// 2D z / u: 1 = interleaved per vertex slot (admm_common.h zu_*), 0 = two arrays (kept:
 // interleaved measured slower, C3 x-update 0.063 -> 0.068 ms, prox 0.325 -> 0.330 ms; profiles/r05/ab/)
 #ifndef MMX_ZU_INTER
 #define MMX_ZU_INTER 0
@@ -36,7 +36,7 @@
 
 namespace mmx {
 // the partial-sum record of a workgroup (admm_kernels.h) and the Bkinv wave block of bidx<D>
-// (admm_kernels.hip; the engine's host mirror bIndex) are part of the word too
+// (admm_prox_common.h; the engine's host mirror bIndex) are part of the word too
 constexpr unsigned kLayoutPartials = 6;
 constexpr unsigned kLayoutBkinvBlock = 64;
 constexpr unsigned kLayoutWord = 0x4d000000u | ((unsigned)(MMX_ZU_INTER != 0) << 0) |

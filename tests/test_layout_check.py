@@ -69,6 +69,21 @@ def _mismatched_lib():
     return lib
 
 
+def _mismatched_kernel_lib():
+    """The smallest ADMM kernel object (admm_kernels_util) rebuilt with MMX_ZU_INTER=1, linked with the
+    default objects."""
+    os.makedirs(OUT, exist_ok=True)
+    lib = os.path.join(OUT, "libmmadmm_kmismatch.so")
+    obj = os.path.join(OUT, "admm_kernels_util_zuinter.o")
+    flags = ["--offload-arch=gfx950", "-std=c++17", "-O1", "-fPIC", "-ffp-contract=off", "-DMMX_ZU_INTER=1"]
+    subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-c", os.path.join(PKG, "csrc", "kernels", "admm_kernels_util.hip"),
+                    "-o", obj], check=True, capture_output=True)
+    objs = [o for o in sorted(glob.glob(os.path.join(BUILD, "*.o"))) if os.path.basename(o) != "admm_kernels_util.o"]
+    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fopenmp", "-o", lib] + objs + [obj] +
+                   ["-Wl,-rpath,/opt/rocm/lib", "-lrccl"], check=True, capture_output=True)
+    return lib, obj
+
+
 def test_consistent_library_passes_the_check():
     import mmadmm_amd as mx
     w = ctypes.c_uint(0)
@@ -95,3 +110,21 @@ def test_mismatched_objects_fail_at_create():
     good = _run_create(os.path.join(PKG, "lib", "libmmadmm.so"))
     rc2, msg2 = good["CREATE"].split(" ", 1)
     assert "layout mismatch" not in msg2 and int(rc2) in (0, 2), good
+
+
+def test_mismatched_stage_kernel_object_fails_at_create():
+    """Every admm_kernels_* stage object is in the check: one of them alone built with another layout
+    switch is named by the failure."""
+    if not os.path.exists(os.path.join(BUILD, "admm_kernels_util.o")):
+        pytest.skip("library objects not built (run __graft_entry__.build())")
+    lib, obj = _mismatched_kernel_lib()
+    try:
+        out = _run_create(lib)
+    finally:  # test artefacts: not left in the tree
+        for f in (lib, obj):
+            if os.path.exists(f):
+                os.remove(f)
+    assert out["LAYOUT"].split()[0] == "1"  # the stand-alone check sees the same object
+    rc, msg = out["CREATE"].split(" ", 1)
+    assert int(rc) == 1, out  # MMADMM_ERR_INVALID, before any HIP call
+    assert "buffer layout mismatch" in msg and "the admm_kernels_util kernel object" in msg, msg
