@@ -315,8 +315,11 @@ class Engine final : public EngineBase {
     if (resH_) (void)hipHostFree(resH_);
     if (evProx_) (void)hipEventDestroy(evProx_);
     if (evEx_) (void)hipEventDestroy(evEx_);
-    if (st2_) (void)hipStreamDestroy(st2_);
-    if (st_) (void)hipStreamDestroy(st_);
+    for (hipStream_t s : {st2_, st_})
+      if (s) {
+        staging_forget(s);
+        (void)hipStreamDestroy(s);
+      }
   }
 
   // MeshIntegrator<D>::step (src/MeshIntegrator.cpp:101-191)

@@ -409,6 +409,7 @@ struct SparseMatrix {
     if (evSpin) (void)hipEventDestroy(evSpin);
     if (h_sc) (void)hipHostFree(h_sc);
     if (h_asc) (void)hipHostFree(h_asc);
+    if (st) staging_forget(st);
     if (st) (void)hipStreamDestroy(st);
   }
 

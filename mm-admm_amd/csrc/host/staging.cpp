@@ -3,6 +3,15 @@
 // ~3-5 GB/s on the box (C4: ~1.5 GB of sweep stages and factor tables, ~0.4 s of the first
 // backward-Euler step); here the source is copied into one of two pinned 32 MB buffers by the
 // host threads while the other one's DMA runs.  Pairs of buffers are pooled per concurrent caller.
+//
+// A pair's events stay pending after the upload returns, so an event can outlive the stream it was
+// recorded on.  The runtime's hipEventSynchronize looks at that stream again (its capture state): on
+// a destroyed stream it reads freed memory, and returned "operation not permitted on an event last
+// recorded in a capturing stream" once that memory had been reused (seen after a few hundred small
+// matrices had been created and destroyed behind a large one).  So no event is waited for after its
+// stream has gone: a pair remembers its stream, staging_forget(stream) settles the idle pairs of a
+// stream about to be destroyed, and a pair taken over for another stream is settled while the
+// pool's lock keeps staging_forget, and with it the stream's destruction, out.
 #include <omp.h>
 
 #include <algorithm>
@@ -22,16 +31,33 @@ struct Staging {
   char* buf[2] = {nullptr, nullptr};
   hipEvent_t ev[2] = {nullptr, nullptr};
   bool pending[2] = {false, false};
+  hipStream_t last = nullptr;  // the stream the pending events were recorded on
+  void settle() {              // (that stream is alive: see above)
+    for (int k = 0; k < 2; ++k)
+      if (pending[k]) {
+        MMX_HIP(hipEventSynchronize(ev[k]));
+        pending[k] = false;
+      }
+  }
 };
 std::mutex g_mu;
 std::vector<Staging*> g_free;
 
-Staging* acquire() {
+Staging* acquire(hipStream_t st) {
   {
     std::lock_guard<std::mutex> lk(g_mu);
     if (!g_free.empty()) {
-      Staging* s = g_free.back();
-      g_free.pop_back();
+      // a pair last used on this stream if there is one (its events are this caller's to wait for)
+      size_t at = g_free.size() - 1;
+      for (size_t i = g_free.size(); i-- > 0;)
+        if (g_free[i]->last == st) {
+          at = i;
+          break;
+        }
+      Staging* s = g_free[at];
+      if (s->last != st) s->settle();  // (a throw leaves the pair in the pool)
+      g_free.erase(g_free.begin() + (long)at);
+      s->last = st;
       return s;
     }
   }
@@ -40,6 +66,7 @@ Staging* acquire() {
     MMX_HIP(hipHostMalloc((void**)&s->buf[k], Staging::kChunk, hipHostMallocDefault));
     MMX_HIP(hipEventCreateWithFlags(&s->ev[k], hipEventDisableTiming));
   }
+  s->last = st;
   return s;
 }
 void give_back(Staging* s) {
@@ -48,9 +75,22 @@ void give_back(Staging* s) {
 }
 }  // namespace
 
+void staging_forget(hipStream_t st) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  for (Staging* s : g_free)
+    if (s->last == st) {
+      for (int k = 0; k < 2; ++k)
+        if (s->pending[k]) {
+          (void)hipEventSynchronize(s->ev[k]);  // (from destructors: nothing to report to)
+          s->pending[k] = false;
+        }
+      s->last = nullptr;
+    }
+}
+
 void upload_staged(void* dst, const void* src, size_t bytes, hipStream_t st) {
   constexpr size_t kChunk = Staging::kChunk;
-  Staging* sg = acquire();
+  Staging* sg = acquire(st);
   struct Back {  // the pair goes back to the pool on every way out (its events guard its chunks)
     Staging* s;
     ~Back() { give_back(s); }

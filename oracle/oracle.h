@@ -81,6 +81,12 @@ int orc_la_ilu_solve(int n, const int* ia, const int* ja, const double* af, cons
 int orc_la_solve(int n, const int* ia, const int* ja, const double* a, const double* b, const double* toler,
                  int nitmax, double resid_reduc, int new_rhat, int initial_guess, double* x, int* nitr,
                  double* rms_hist, int dotMode);
+/* ILU(k): the factor and the sweeps in the factor pattern (iaf, jaf); A's rows may be unsorted */
+int orc_la_ilu_level(int n, const int* ia, const int* ja, const double* a, const int* iaf, const int* jaf,
+                     double* af);
+int orc_la_solve_level(int n, const int* ia, const int* ja, const double* a, const int* iaf, const int* jaf,
+                       const double* b, const double* toler, int nitmax, double resid_reduc, int new_rhat,
+                       int initial_guess, double* x, int* nitr, double* rms_hist, int dotMode);
 
 #ifdef __cplusplus
 }

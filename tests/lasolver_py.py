@@ -38,6 +38,8 @@ def orc():
         _orc.orc_la_ilu0.argtypes = [_i, _ip, _ip, _dp, _dp]
         _orc.orc_la_ilu_solve.argtypes = [_i, _ip, _ip, _dp, _dp, _dp]
         _orc.orc_la_solve.argtypes = [_i, _ip, _ip, _dp, _dp, _dp, _i, _d, _i, _i, _dp, _ip, _dp, _i]
+        _orc.orc_la_ilu_level.argtypes = [_i, _ip, _ip, _dp, _ip, _ip, _dp]
+        _orc.orc_la_solve_level.argtypes = [_i, _ip, _ip, _dp, _ip, _ip, _dp, _dp, _i, _d, _i, _i, _dp, _ip, _dp, _i]
     return _orc
 
 
@@ -120,6 +122,17 @@ def ilu0(ia, ja, a):
     return af
 
 
+def ilu_level(ia, ja, a, iaf, jaf):
+    """The numeric ILU(k) in the factor pattern (iaf, jaf): A's values scattered into it row by row in
+    A's storage order (fill 0.0), then the reference's factor.  A's rows may be unsorted."""
+    n = len(ia) - 1
+    ia, ja, a, iaf, jaf = _i32(ia), _i32(ja), _f64(a), _i32(iaf), _i32(jaf)
+    af = np.zeros(len(jaf))
+    assert orc().orc_la_ilu_level(n, _ptr(ia, _ip), _ptr(ja, _ip), _ptr(a, _dp), _ptr(iaf, _ip), _ptr(jaf, _ip),
+                                  _ptr(af, _dp)) == 0
+    return af
+
+
 def ref_ilu(ia, ja, a, level=0):
     """The reference's own ILU factor (sfac2 + factor) -> (iaf, jaf, af, diag row-relative)."""
     n = len(ia) - 1
@@ -151,9 +164,12 @@ def ilu_solve(ia, ja, af, b):
     return x
 
 
-def solve(ia, ja, a, b, nitmax=10000, resid_reduc=1e-6, new_rhat=0, x0=None, toler=None, use_ref=False, tree=False):
+def solve(ia, ja, a, b, nitmax=10000, resid_reduc=1e-6, new_rhat=0, x0=None, toler=None, use_ref=False, tree=False,
+          iaf=None, jaf=None):
     """MatrixIter::solve with the src/Mesh.cpp parameters -> (x, nitr, rms history).
-    tree=True: dot products in the GPU's fixed reduction order instead of sequential sums."""
+    tree=True: dot products in the GPU's fixed reduction order instead of sequential sums.
+    iaf, jaf: the ILU(k) factor pattern (the factor and the sweeps run on it, matmult on A's own
+    pattern in storage order); default: A's pattern, level 0."""
     n = len(ia) - 1
     ia, ja, a, b = _i32(ia), _i32(ja), _f64(a), _f64(b)
     tol = _f64(toler) if toler is not None else None
@@ -166,9 +182,16 @@ def solve(ia, ja, a, b, nitmax=10000, resid_reduc=1e-6, new_rhat=0, x0=None, tol
         assert rc == 0
         return x, nitr.value, None
     hist = np.zeros(max(nitmax, 1))
-    rc = orc().orc_la_solve(n, _ptr(ia, _ip), _ptr(ja, _ip), _ptr(a, _dp), _ptr(b, _dp), _ptr(tol, _dp),
-                            nitmax, resid_reduc, new_rhat, 1 if x0 is not None else 0, _ptr(x, _dp),
-                            ctypes.byref(nitr), _ptr(hist, _dp), 1 if tree else 0)
+    if iaf is not None:
+        iaf, jaf = _i32(iaf), _i32(jaf)
+        rc = orc().orc_la_solve_level(n, _ptr(ia, _ip), _ptr(ja, _ip), _ptr(a, _dp), _ptr(iaf, _ip), _ptr(jaf, _ip),
+                                      _ptr(b, _dp), _ptr(tol, _dp), nitmax, resid_reduc, new_rhat,
+                                      1 if x0 is not None else 0, _ptr(x, _dp), ctypes.byref(nitr), _ptr(hist, _dp),
+                                      1 if tree else 0)
+    else:
+        rc = orc().orc_la_solve(n, _ptr(ia, _ip), _ptr(ja, _ip), _ptr(a, _dp), _ptr(b, _dp), _ptr(tol, _dp),
+                                nitmax, resid_reduc, new_rhat, 1 if x0 is not None else 0, _ptr(x, _dp),
+                                ctypes.byref(nitr), _ptr(hist, _dp), 1 if tree else 0)
     assert rc == 0
     k = nitr.value if nitr.value > 0 else nitmax
     return x, nitr.value, hist[:k]
