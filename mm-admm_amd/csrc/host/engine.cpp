@@ -19,6 +19,7 @@
 #include "comm.h"
 #include "common.h"
 #include "partition.h"
+#include "xup_records.h"
 
 #define MMX_SP(expr)                                                                     \
   do {                                                                                   \
@@ -204,6 +205,8 @@ class Engine final : public EngineBase {
       overlap_ = nranks_ > 1 && !(ov && atoi(ov) == 0);
       const char* fp = getenv("MMX_FUSE_PRED");  // 0: k_predict runs in every step (DeviceMesh::predBar)
       fusePred_ = !(fp && atoi(fp) == 0);
+      const char* gk = getenv("MMX_GC_SKIP");
+      gcSkip_ = !(gk && atoi(gk) == 0);
       if (tslotOn_) tslot_.alloc(std::max<size_t>((size_t)nF_ * K, 1));
     }
     {  // x-update order: nodes by their first incident (local) simplex, then id -- locality of the
@@ -247,6 +250,24 @@ class Engine final : public EngineBase {
       std::vector<int32_t> ord(inner);
       ord.insert(ord.end(), bound.begin(), bound.end());
       nodeOrder_.upload(ord.data(), std::max<size_t>(ord.size(), 1), st_);
+      // the same order as records (xup_records.h): the x-update's fixed data by position, so a lane
+      // reaches its z/u gathers in two dependent load phases instead of four; MMX_XUP_REC=0: the CSR
+      const char* xr = getenv("MMX_XUP_REC");
+      xupRec_ = !(xr && atoi(xr) == 0);
+      XupRecords recs;
+      if (xupRec_) {
+        // columns: the widest chunk a kernel of this dimension may take (a narrower one reads a prefix)
+        const int ch = std::max(D == 2 ? MMX_XU_CH2D : 8, xupChunk());
+        recs = build_xup_records(nl, ord.data(), plan_.incPtr.data(), plan_.incSrc.data(), invdiag.data(), ch);
+        xrec_.upload(recs.rec.data(), recs.rec.size(), st_);
+        xinv_.upload(recs.invdiag.data(), recs.invdiag.size(), st_);
+        xslot_.upload(recs.slot.data(), recs.slot.size(), st_);
+        xslotStride_ = (int)recs.stride;
+        xslotCh_ = ch;
+        const int chs = D == 2 ? MMX_XU_CH2D : xupChunk();  // the steady loop's chunk: slots past it come from inc_off
+        xupTail_ = 0;
+        for (int v = 0; v < nl; ++v) xupTail_ += std::max(0, plan_.incPtr[v + 1] - plan_.incPtr[v] - chs);
+      }
       streamWait();
     }
     invdiag_.upload(invdiag.data(), invdiag.size(), st_);
@@ -403,11 +424,14 @@ class Engine final : public EngineBase {
         tiePar_ ^= 1;
         std::swap(m_.tieCount, m_.tieStale);
       }
+      // a step's last prox: the next step resets z, so nothing reads the gradient cache it would leave
+      // (2D; MMX_GC_SKIP=0: written as in every other prox)
+      m_.gcSkip = (D == 2 && gcSkip_ && !early && i == nIters - 1) ? 1 : 0;
       launch_prox<D>(m_, !hessComputed_, gcacheValid_, early ? tol / 100 : 1e-3 / 100, x_.p, z_.p, uPtr(), B_.p,
                      swapB ? B2_.p : B_.p, partA_.p + (deferRed ? slice * i : 0), &nbp, st_);
       m_.zx = nullptr;  // z is in z_ from the first prox on
       if (swapB) std::swap(B_.p, B2_.p);
-      gcacheValid_ = true;  // the prox's last blockGrad left the gradient at the final z
+      gcacheValid_ = !m_.gcSkip;  // the prox's last blockGrad left the gradient at the final z
       if (timing) {
         a1 = nextEvent();
         MMX_HIP(hipEventRecord(a1, st_));
@@ -737,7 +761,13 @@ class Engine final : public EngineBase {
     const double ts = tslotOn_ ? 1.0 : 0.0;
     s->prox_bytes = nF * (4.0 * (D + 1) + 1 + 8.0 * (2 * K + K * K) * 2 + 8.0 * K * 2 + ts * 8.0 * K) +
                     nP * 8.0 * D;
-    s->xupdate_bytes = 4.0 * (nP + 1) + 4.0 * (D + 1) * nF + (16.0 - 8.0 * ts) * K * nF + 8.0 * D * nP * 2 + 8.0 * nP;
+    // on the records (xup_records.h) the x-update reads, by position, the record (12 B), invdiag (8 B)
+    // and the steady loop's chunk of the slot table (4 CH B), and from the CSR only the offsets of the
+    // slots past a node's first CH; MMX_XUP_REC=0: inc_ptr, inc_off and invdiag by node
+    const double ch = D == 2 ? MMX_XU_CH2D : xupChunk();
+    const double fixed = xupRec_ ? nP * (4.0 * kXupRecInts + 8.0 + 4.0 * ch) + 4.0 * (double)xupTail_
+                                 : 4.0 * (nP + 1) + 4.0 * (D + 1) * nF + 8.0 * nP;
+    s->xupdate_bytes = fixed + (16.0 - 8.0 * ts) * K * nF + 8.0 * D * nP * 2;
     s->monitor_iso = iso_ ? 1 : 0;
     s->halo_send_bytes = 8.0 * D * (double)plan_.sendOff.size();
     s->halo_recv_bytes = nranks_ > 1 ? 8.0 * D * (double)plan_.recvRows : 0.0;
@@ -1458,6 +1488,14 @@ class Engine final : public EngineBase {
     st_stats_.regrids += 1;
   }
 
+  // slots requested at once per node in the slot-term sweep: MMX_XUP_CH as the launch reads it (8, 16, 24)
+  static int xupChunk() {
+    const char* xc = getenv("MMX_XUP_CH");
+    const int c = xc ? atoi(xc) : 8;
+    return c >= 24 ? 24 : c >= 16 ? 16 : 8;
+  }
+  static constexpr int kXupEarlyDefault = 1;  // (C4 0.1421 against 0.1423 ms without, 0.1452 from the CSR)
+
   DeviceMesh<D> makeView() const {
     DeviceMesh<D> m{};
     m.nP = nP_;
@@ -1480,9 +1518,20 @@ class Engine final : public EngineBase {
     m.prox2dWave = wave2d_ ? 1 : 0;
     {
       const char* xs = getenv("MMX_XUP_SWEEP");  // 3D default: one workgroup per CU (profiles/r03/xupdate)
-      m.xupSweep = xs ? std::max(0, atoi(xs)) : (D == 3 ? 1 : 0);
-      const char* xc = getenv("MMX_XUP_CH");
-      m.xupCh = xc ? atoi(xc) : 8;
+      // 2D on the records: two workgroups per CU with the early request (C3 0.0568 against 0.0596 ms one
+      // node per lane from the CSR, C2 0.0075 against 0.0082); from the CSR one node per lane
+      m.xupSweep = xs ? std::max(0, atoi(xs)) : (D == 3 ? 1 : (xupRec_ ? 2 : 0));
+      m.xupCh = xupChunk();
+      // the records' sweep with the next node requested early (MMX_XUP_EARLY=0/1)
+      const char* xe = getenv("MMX_XUP_EARLY");
+      m.xupEarly = xe ? atoi(xe) != 0 : kXupEarlyDefault;
+    }
+    if (xupRec_) {
+      m.xrec = xrec_.p;
+      m.xinv = xinv_.p;
+      m.xslot = xslot_.p;
+      m.xslotStride = xslotStride_;
+      m.xslotCh = xslotCh_;
     }
     {
       const char* ft = getenv("MMX_FORCE_TIE");
@@ -1628,6 +1677,11 @@ class Engine final : public EngineBase {
   DevBuf<double> partA_, partB_, results_, export_, remote_, resAll_, redScratch_;
   RedWork red_;  // the split reductions' work space (launch_reduce_*)
   DevBuf<int32_t> expOff_, tieList_, nodeOrder_;
+  DevBuf<int32_t> xrec_, xslot_;  // the x-update's node records (xup_records.h)
+  DevBuf<double> xinv_;
+  int xslotStride_ = 0, xslotCh_ = 0;
+  long long xupTail_ = 0;  // incident slots past their node's first chunk (stats)
+  bool xupRec_ = true, gcSkip_ = true;
   bool wave2d_ = false;  // 2D prox through k_prox_wave<2> (double-buffered Bkinv)
   DevBuf<unsigned> tieCount_;
   int tiePar_ = 0;

@@ -51,7 +51,18 @@ struct DeviceMesh {
   // interior nodes, which need no remote slot, while the halo exchange runs, then the rest)
   int xupLo, xupHi;
   const double* invdiag;  // per node 1 / t_ii (block-diagonal t = tau I + dt^2 WD^T WD)
-  const double* Vc;       // nP x D reference positions (CompMesh) or nullptr
+  // the x-update's node records by position p of the node order (host/xup_records.h; nullptr: the
+  // kernels walk nodeOrder / inc_ptr / inc_off, MMX_XUP_REC=0): xrec[3 p ..] = {v, b, e}, xinv[p] =
+  // invdiag[v], xslot[j xslotStride + p] = the node's j-th incident-slot offset, j < xslotCh
+  const int* xrec;
+  const double* xinv;
+  const int* xslot;
+  int xslotStride, xslotCh;
+  int xupEarly;           // sweep on the records: a lane requests its next node's record before its gathers
+  // set for a step's last prox (early exit off): its BFGS loop does not write the gradient cache, which
+  // the next step never reads (its z is reset)
+  int gcSkip;
+  const double* Vc;      // nP x D reference positions (CompMesh) or nullptr
   // monitor grid
   const double* gx;
   const double* gy;

@@ -683,7 +683,8 @@ __global__ void __launch_bounds__(BS, 2) k_prox_lds(DeviceMesh<D> m, double tol,
     LdsB<K, 64> Bacc{lds + (tid >> 6) * KK * 64 + (tid & 63)};
     const int its =
         tie ? 0
-            : bfgs_iterations<D, LdsB<K, 64>, false, kHint>(Bacc, g, fc, z, xi, dx, G, fixedBits, tol, bad, gc, &tie,
+            : bfgs_iterations<D, LdsB<K, 64>, false, kHint>(Bacc, g, fc, z, xi, dx, G, fixedBits, tol, bad,
+                                                            m.gcSkip ? nullptr : m.gcache + (size_t)s * K, &tie,
                                                             kHint ? &hint : nullptr);
 #ifdef MMX_HINT_PROBE
     if constexpr (kHint) pv[2] = (double)hint.hits;  // probe build: the prox leaves partial 2 unused

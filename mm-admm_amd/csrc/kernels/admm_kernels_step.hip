@@ -83,21 +83,50 @@ __global__ void __launch_bounds__(kBlock) k_predict(DeviceMesh<D> m, int mode, c
 
 // x-update: vec = tau*xBar + dt^2 WD_T (w (z - u)), x = vec / t_vv (block-diagonal t),
 // optional |D x - z|^2 partial sums (primal residual, src/MeshIntegrator.cpp:162).
-// A node's incident slots are taken 8 at a time: their offsets, then all their z and u values
+// A node's incident slots are taken CH at a time: their offsets, then all their z and u values
 // are requested before the first is added (branch-free: lanes past the end re-read the last
 // slot, a slot of another rank reads its gathered row), then summed in ascending order.
+//
+// XupHead: what a lane knows of its node before the first gather -- the node, its slot range,
+// invdiag and the first CH slot offsets.  From the records (DeviceMesh::xrec, host/xup_records.h)
+// every address follows from the position, so the head is one load phase and the gathers the
+// second; from the CSR (MMX_XUP_REC=0) it is three dependent phases.
+template <int CH>
+struct XupHead {
+  int v, b, e;
+  double inv;
+  int off[CH];
+};
+template <int D, int CH>
+__device__ __forceinline__ void xup_head_rec(const DeviceMesh<D>& m, int idx, XupHead<CH>& h) {
+  const int* r = m.xrec + (size_t)idx * kXupRecInts;
+  h.v = r[0];
+  h.b = r[1];
+  h.e = r[2];
+  h.inv = m.xinv[idx];
+#pragma unroll
+  for (int j = 0; j < CH; ++j) h.off[j] = m.xslot[(size_t)j * m.xslotStride + idx];
+}
+template <int D, int CH>
+__device__ __forceinline__ void xup_head_csr(const DeviceMesh<D>& m, int idx, XupHead<CH>& h) {
+  // processing order: nodes by first incident simplex, so a workgroup's nodes share simplices
+  h.v = m.nodeOrder ? m.nodeOrder[idx] : idx;
+  h.b = m.inc_ptr[h.v];
+  h.e = m.inc_ptr[h.v + 1];
+  h.inv = m.invdiag[h.v];
+#pragma unroll
+  for (int j = 0; j < CH; ++j) h.off[j] = (h.e > h.b) ? m.inc_off[min(h.b + j, h.e - 1)] : 0;
+}
 template <int D, bool RESID, bool TS, int CH = 8, bool ZX = false, bool PRED = false, bool REM = false>
 __device__ __forceinline__ void xupdate_node(const DeviceMesh<D>& m, const StepScalars& sc,
                                              const double* __restrict__ xBar, const double* __restrict__ z,
-                                             const double* __restrict__ u, double* __restrict__ x, int idx,
-                                             double (&pv)[3]) {
+                                             const double* __restrict__ u, double* __restrict__ x,
+                                             const XupHead<CH>& h, double (&pv)[3]) {
   {
-    // processing order: nodes by first incident simplex, so a workgroup's nodes share simplices
-    const int v = m.nodeOrder ? m.nodeOrder[idx] : idx;
+    const int v = h.v, b = h.b, e = h.e;
     double acc[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) acc[c] = 0.0;
-    const int b = m.inc_ptr[v], e = m.inc_ptr[v + 1];
     double xb[D], zn[D];
     if constexpr (PRED) {  // predictX mode 1 for this node (k_predict): xBar = 2 x - xPrev, xPrev = x
       double xv[D];
@@ -128,11 +157,9 @@ __device__ __forceinline__ void xupdate_node(const DeviceMesh<D>& m, const StepS
         for (int c = 0; c < D; ++c) zn[c] = m.zx[(size_t)v * D + c];
       }
     }
-    const double inv = m.invdiag[v];
-    for (int t0 = b; t0 < e; t0 += CH) {
-      int off[CH];
-#pragma unroll
-      for (int j = 0; j < CH; ++j) off[j] = m.inc_off[min(t0 + j, e - 1)];
+    const double inv = h.inv;
+    // one chunk: the slots t0 .. t0 + CH - 1 at the offsets off
+    auto addChunk = [&](int t0, const int(&off)[CH]) {
       double zv[CH][D], uv[CH][D];
 #pragma unroll
       for (int j = 0; j < CH; ++j) {
@@ -168,6 +195,14 @@ __device__ __forceinline__ void xupdate_node(const DeviceMesh<D>& m, const StepS
           }
         }
       }
+    };
+    // the first chunk's offsets came with the head; the rest (a node of more than CH slots) from the CSR
+    if (b < e) addChunk(b, h.off);
+    for (int t0 = b + CH; t0 < e; t0 += CH) {
+      int off[CH];
+#pragma unroll
+      for (int j = 0; j < CH; ++j) off[j] = m.inc_off[min(t0 + j, e - 1)];
+      addChunk(t0, off);
     }
     double xn[D];
 #pragma unroll
@@ -177,10 +212,7 @@ __device__ __forceinline__ void xupdate_node(const DeviceMesh<D>& m, const StepS
     }
     if constexpr (RESID) {  // same chunking; a slot of another rank is counted by its owner
       double r2 = 0.0;
-      for (int t0 = b; t0 < e; t0 += CH) {
-        int off[CH];
-#pragma unroll
-        for (int j = 0; j < CH; ++j) off[j] = m.inc_off[min(t0 + j, e - 1)];
+      auto residChunk = [&](int t0, const int(&off)[CH]) {
         double zv[CH][D];
 #pragma unroll
         for (int j = 0; j < CH; ++j) {
@@ -198,25 +230,40 @@ __device__ __forceinline__ void xupdate_node(const DeviceMesh<D>& m, const StepS
             }
           }
         }
+      };
+      if (b < e) residChunk(b, h.off);  // (the offsets it already holds)
+      for (int t0 = b + CH; t0 < e; t0 += CH) {
+        int off[CH];
+#pragma unroll
+        for (int j = 0; j < CH; ++j) off[j] = m.inc_off[min(t0 + j, e - 1)];
+        residChunk(t0, off);
       }
       pv[2] = r2;
     }
   }
 }
-#ifndef MMX_XU_CH2D
-#define MMX_XU_CH2D 6  // 2D: incident slots requested at once per node (C3: 8 0.066 ms, 6 0.0645, 4 0.079)
-#endif
-template <int D, bool RESID, bool TS, bool ZX = false, bool PRED = false, bool REM = false>
+template <int D, int CH, bool REC>
+__device__ __forceinline__ void xup_head(const DeviceMesh<D>& m, int idx, XupHead<CH>& h) {
+  if constexpr (REC)
+    xup_head_rec<D, CH>(m, idx, h);
+  else
+    xup_head_csr<D, CH>(m, idx, h);
+}
+template <int D, bool RESID, bool TS, bool ZX = false, bool PRED = false, bool REM = false, bool REC = false>
 __global__ void __launch_bounds__(kBlock) k_xupdate(DeviceMesh<D> m, StepScalars sc,
                                                      const double* __restrict__ xBar,
                                                      const double* __restrict__ z,
                                                      const double* __restrict__ u, double* __restrict__ x,
                                                      double* __restrict__ partials, int xcd) {
+  constexpr int CH = (D == 2 ? MMX_XU_CH2D : 8);
   const int lb = logical_block(xcd);
   const int idx = m.xupLo + lb * kBlock + threadIdx.x;
   double pv[3] = {0, 0, 0};
-  if (idx < m.xupHi)
-    xupdate_node<D, RESID, TS, (D == 2 ? MMX_XU_CH2D : 8), ZX, PRED, REM>(m, sc, xBar, z, u, x, idx, pv);
+  if (idx < m.xupHi) {
+    XupHead<CH> h;
+    xup_head<D, CH, REC>(m, idx, h);
+    xupdate_node<D, RESID, TS, CH, ZX, PRED, REM>(m, sc, xBar, z, u, x, h, pv);
+  }
   if constexpr (RESID) block_partials<3>(pv, partials, lb);
 }
 // The slot-term x-update (no residual) as a sweep: XCD c (= blockIdx % 8) takes the node-order
@@ -227,17 +274,37 @@ __global__ void __launch_bounds__(kBlock) k_xupdate(DeviceMesh<D> m, StepScalars
 // RESID: the primal residual too (a step's last iteration, or every iteration with the early exit):
 // each lane sums its nodes' terms in its round order and the workgroup's partial record is
 // blockIdx.x -- a fixed grouping for a fixed grid, so runs are bit-reproducible
-template <int D, bool TS, int CH, bool RESID = false>
+// EARLY (on the records): a lane requests the head of its next position before it waits for the
+// current node's gathers -- loads return in order, so the head has arrived when the gathers have,
+// and one exposed load phase per node is left
+template <int D, bool TS, int CH, bool RESID = false, bool REC = false, bool EARLY = false>
 __global__ void __launch_bounds__(kBlock) k_xupdate_sweep(DeviceMesh<D> m, StepScalars sc,
                                                            const double* __restrict__ xBar,
                                                            const double* __restrict__ z, const double* __restrict__ u,
                                                            double* __restrict__ x, int n8, double* __restrict__ partials) {
+  static_assert(REC || !EARLY, "the early request reads the records");
   const int c = (int)(blockIdx.x % 8), w = (int)(blockIdx.x / 8), per = (int)(gridDim.x / 8);
   const int lo = m.xupLo + c * n8, hi = min(lo + n8, m.xupHi);
   double pv[3], r2 = 0.0;
-  for (int idx = lo + w * kBlock + (int)threadIdx.x; idx < hi; idx += per * kBlock) {
-    xupdate_node<D, RESID, TS, CH>(m, sc, xBar, z, u, x, idx, pv);
-    if constexpr (RESID) r2 += pv[2];
+  int idx = lo + w * kBlock + (int)threadIdx.x;
+  if constexpr (EARLY) {
+    XupHead<CH> cur, nxt;
+    if (idx < hi) xup_head<D, CH, true>(m, idx, cur);
+    nxt = cur;
+    for (; idx < hi; idx += per * kBlock) {
+      if (idx + per * kBlock < hi) xup_head<D, CH, true>(m, idx + per * kBlock, nxt);
+      __builtin_amdgcn_sched_barrier(0);  // (the next head's loads stay ahead of this node's gathers)
+      xupdate_node<D, RESID, TS, CH>(m, sc, xBar, z, u, x, cur, pv);
+      if constexpr (RESID) r2 += pv[2];
+      cur = nxt;
+    }
+  } else {
+    for (; idx < hi; idx += per * kBlock) {
+      XupHead<CH> h;
+      xup_head<D, CH, REC>(m, idx, h);
+      xupdate_node<D, RESID, TS, CH>(m, sc, xBar, z, u, x, h, pv);
+      if constexpr (RESID) r2 += pv[2];
+    }
   }
   if constexpr (RESID) {
     double q[3] = {0.0, 0.0, r2};
@@ -464,11 +531,19 @@ void launch_xupdate(const DeviceMesh<D>& m, const StepScalars& sc, const double*
   }
   const bool ts = useTslot && m.tslot;
   const bool rem = m.remote != nullptr;
+  const bool rec = m.xrec != nullptr;  // the node records (MMX_XUP_REC=0: the CSR)
+  auto needCols = [&](int ch) {  // a kernel's first chunk is the table's first ch columns
+    if (rec && m.xslotCh < ch) throw std::logic_error("launch_xupdate: the slot table has fewer columns than the chunk");
+  };
   if (m.zx && !resid && !ts) {  // a step's first x-update: z from DeviceMesh::zx
+    needCols(D == 2 ? MMX_XU_CH2D : 8);
     dispatch_bool(m.predBar != nullptr, [&](auto pred) {  // ... and predictX's extrapolation fused in
       dispatch_bool(rem, [&](auto r) {
-        hipLaunchKernelGGL((k_xupdate<D, false, false, true, decltype(pred)::value, decltype(r)::value>), dim3(*nblocks),
-                           dim3(kBlock), 0, st, m, sc, xBar, z, u, x, partials, xcd_map());
+        dispatch_bool(rec, [&](auto rc) {
+          hipLaunchKernelGGL(
+              (k_xupdate<D, false, false, true, decltype(pred)::value, decltype(r)::value, decltype(rc)::value>),
+              dim3(*nblocks), dim3(kBlock), 0, st, m, sc, xBar, z, u, x, partials, xcd_map());
+        });
       });
     });
     return;
@@ -483,25 +558,42 @@ void launch_xupdate(const DeviceMesh<D>& m, const StepScalars& sc, const double*
   if (m.xupSweep > 0 && (!resid || sweepResid)) {
     const int n8 = ((nsub + kBlock - 1) / kBlock + 7) / 8 * kBlock;  // = the node order's XCD groups
     const dim3 g(256 * m.xupSweep);
+    // on the records, with or without the next node's early request (DeviceMesh::xupEarly); else the CSR
+    auto sweep = [&](auto tsT, auto chT, auto residT, double* part) {
+      constexpr bool TS = decltype(tsT)::value, RS = decltype(residT)::value;
+      constexpr int CH = decltype(chT)::value;
+      needCols(CH);
+      if (rec && m.xupEarly)
+        hipLaunchKernelGGL((k_xupdate_sweep<D, TS, CH, RS, true, true>), g, dim3(kBlock), 0, st, m, sc, xBar, z, u, x, n8,
+                           part);
+      else if (rec)
+        hipLaunchKernelGGL((k_xupdate_sweep<D, TS, CH, RS, true, false>), g, dim3(kBlock), 0, st, m, sc, xBar, z, u, x, n8,
+                           part);
+      else
+        hipLaunchKernelGGL((k_xupdate_sweep<D, TS, CH, RS>), g, dim3(kBlock), 0, st, m, sc, xBar, z, u, x, n8, part);
+    };
+    using T = std::true_type;
+    using F = std::false_type;
     if (sweepResid) {
       *nblocks = (int)g.x;
-      hipLaunchKernelGGL((k_xupdate_sweep<D, true, 8, true>), g, dim3(kBlock), 0, st, m, sc, xBar, z, u, x, n8,
-                         partials);
+      sweep(T{}, std::integral_constant<int, 8>{}, T{}, partials);
     } else if (ts && m.xupCh >= 24)
-      hipLaunchKernelGGL((k_xupdate_sweep<D, true, 24>), g, dim3(kBlock), 0, st, m, sc, xBar, z, u, x, n8, nullptr);
+      sweep(T{}, std::integral_constant<int, 24>{}, F{}, nullptr);
     else if (ts && m.xupCh >= 16)
-      hipLaunchKernelGGL((k_xupdate_sweep<D, true, 16>), g, dim3(kBlock), 0, st, m, sc, xBar, z, u, x, n8, nullptr);
+      sweep(T{}, std::integral_constant<int, 16>{}, F{}, nullptr);
     else if (ts)
-      hipLaunchKernelGGL((k_xupdate_sweep<D, true, 8>), g, dim3(kBlock), 0, st, m, sc, xBar, z, u, x, n8, nullptr);
+      sweep(T{}, std::integral_constant<int, 8>{}, F{}, nullptr);
     else
-      hipLaunchKernelGGL((k_xupdate_sweep<D, false, (D == 2 ? MMX_XU_CH2D : 8)>), g, dim3(kBlock), 0, st, m, sc, xBar,
-                         z, u, x, n8, nullptr);
+      sweep(F{}, std::integral_constant<int, (D == 2 ? MMX_XU_CH2D : 8)>{}, F{}, nullptr);
     return;
   }
+  needCols(D == 2 ? MMX_XU_CH2D : 8);
   dispatch_bool(resid, [&](auto r) {
     dispatch_bool(ts, [&](auto t) {
-      hipLaunchKernelGGL((k_xupdate<D, decltype(r)::value, decltype(t)::value>), dim3(*nblocks), dim3(kBlock), 0, st, m,
-                         sc, xBar, z, u, x, partials, xcd_map());
+      dispatch_bool(rec, [&](auto rc) {
+        hipLaunchKernelGGL((k_xupdate<D, decltype(r)::value, decltype(t)::value, false, false, false, decltype(rc)::value>),
+                           dim3(*nblocks), dim3(kBlock), 0, st, m, sc, xBar, z, u, x, partials, xcd_map());
+      });
     });
   });
 }

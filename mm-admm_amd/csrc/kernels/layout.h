@@ -33,8 +33,18 @@
 #ifndef MMX_CHAIN_CODE16
 #define MMX_CHAIN_CODE16 1
 #endif
+// 2D x-update: incident slots requested at once per node (C3: 8 0.066 ms, 6 0.0645, 4 0.079) -- also the
+// columns of the 2D slot table built on the host (host/xup_records.h)
+#ifndef MMX_XU_CH2D
+#define MMX_XU_CH2D 6
+#endif
 
 namespace mmx {
+// the x-update's node records by position of the node order (host/xup_records.h, built by the engine,
+// read by admm_kernels_step.hip): kXupRecInts ints {v, b, e} per position, and the slot table's
+// columns kXupStridePad-aligned
+constexpr unsigned kXupRecInts = 3;
+constexpr unsigned kXupStridePad = 64;
 // the partial-sum record of a workgroup (admm_kernels.h) and the Bkinv wave block of bidx<D>
 // (admm_prox_common.h; the engine's host mirror bIndex) are part of the word too
 constexpr unsigned kLayoutPartials = 6;
@@ -43,5 +53,7 @@ constexpr unsigned kLayoutWord = 0x4d000000u | ((unsigned)(MMX_ZU_INTER != 0) <<
                                  ((unsigned)(MMX_CHAIN_VEC != 0) << 1) | ((unsigned)(MMX_CHAIN_CODE16 != 0) << 2) |
                                  (((unsigned)MMX_SPMV_TILE / 256u & 0xFu) << 4) |
                                  (((unsigned)MMX_SPMV_BLOCK / 64u & 0xFu) << 8) | ((kLayoutPartials & 0xFu) << 12) |
-                                 ((kLayoutBkinvBlock / 64u & 0x3u) << 16) | ((unsigned)(MMX_B3_PAIRS != 0) << 18);
+                                 ((kLayoutBkinvBlock / 64u & 0x3u) << 16) | ((unsigned)(MMX_B3_PAIRS != 0) << 18) |
+                                 ((unsigned)(kXupRecInts == 3 && kXupStridePad == 64) << 19) |
+                                 (((unsigned)MMX_XU_CH2D & 0xFu) << 20);
 }  // namespace mmx
