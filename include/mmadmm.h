@@ -183,6 +183,10 @@ int mmadmm_sizes(mmadmm_handle h, int* nP, int* nF, int* grid_rows);
 int mmadmm_set_timing(mmadmm_handle h, int on);
 int mmadmm_stats_get(mmadmm_handle h, mmadmm_stats* s);
 int mmadmm_stats_reset(mmadmm_handle h);
+/* The engine's MMX_* run-time switches as resolved when it was created (Run-time
+ * switches), one "MMX_NAME=value" line each, into buf (cap bytes, always 0-terminated; truncated when
+ * cap is too small).  Returns the bytes needed, the terminating 0 included, or -(error code). */
+int mmadmm_options_get(mmadmm_handle h, char* buf, int cap);
 int mmadmm_sync(mmadmm_handle h);
 int mmadmm_destroy(mmadmm_handle h);
 

@@ -161,6 +161,10 @@ int mmx_matrix_get_scale(mmx_matrix m, double* scal);
 int mmx_matrix_set_timing(mmx_matrix m, int on);
 int mmx_matrix_stats_get(mmx_matrix m, mmx_sparse_stats* out);
 int mmx_matrix_stats_reset(mmx_matrix m);
+/* The matrix's MMX_* run-time switches as resolved when it was created (Run-time
+ * switches), one "MMX_NAME=value" line each, into buf (cap bytes, always 0-terminated; truncated when
+ * cap is too small).  Returns the bytes needed, the terminating 0 included, or -(error code). */
+int mmx_matrix_options_get(mmx_matrix m, char* buf, int cap);
 int mmx_matrix_destroy(mmx_matrix m);
 
 /* Host-only symbolic ILU (sfac2 + merge2, lib/LASolver/ILU_class.cpp:17-295), natural order: the
@@ -179,7 +183,7 @@ int mmx_rcm(int n, const int32_t* ia, const int32_t* ja, int32_t* lorder);
 /* Diagnostics (host only): the chain/band schedule the sweeps would use for the ILU(level) of this
  * pattern.  info[16]: ok, E, R, RI, bands, chains, max chain length,
  * max skew, max band iterations, slots, imports, simulated critical iterations, levels. */
-/* Cycle counters of the chain sweeps when MMX_CHAIN_PROF=1 was set before sfac (1024 values:
+/* Cycle counters of the chain sweeps when MMX_CHAIN_PROF=1 was set when the matrix was created (1024 values:
  * forward 0..511, backward 512..1023; layout in chain_sweep.hip); reset != 0 zeroes them. */
 int mmx_matrix_chain_prof(mmx_matrix m, unsigned long long* out, int reset);
 int mmx_sweep_schedule_info(int n, const int32_t* ia, const int32_t* ja, int level, int fwd, long long* info);

@@ -13,12 +13,12 @@
 namespace mmx {
 
 namespace {
-// MMX_SCHED_PROF=1: the builders' phase times on stderr (host set-up of the first backward-Euler step)
+// ChainKnobs::schedProf: the builders' phase times on stderr (host set-up of the first backward-Euler step)
 struct PhaseClock {
   bool on;
   const char* who;
   std::chrono::steady_clock::time_point t;
-  explicit PhaseClock(const char* w) : on(getenv("MMX_SCHED_PROF") != nullptr), who(w), t(std::chrono::steady_clock::now()) {}
+  PhaseClock(bool on_, const char* w) : on(on_), who(w), t(std::chrono::steady_clock::now()) {}
   void mark(const char* what) {
     if (!on) return;
     const auto n = std::chrono::steady_clock::now();
@@ -27,14 +27,6 @@ struct PhaseClock {
   }
 };
 constexpr int kChainLenCap = 1 << 20;  // longest chain (positions fit the schedule's ints)
-// iterations a global value takes to reach another band (model; MMX_CHAIN_LAT overrides)
-static int import_latency() {
-  static int v = [] {
-    const char* e = getenv("MMX_CHAIN_LAT");
-    return e ? std::max(0, atoi(e)) : 8;
-  }();
-  return v;
-}
 int pow2_at_least(int v) {
   int r = 1;
   while (r < v) r <<= 1;
@@ -87,11 +79,13 @@ void big_fill(BigVec& v, size_t n, int x) {
   for (size_t i = 0; i < n; ++i) p[i] = x;
 }
 
-ChainSchedule build_chain_schedule(int n, const std::vector<int>& iaf, const std::vector<int>& jaf,
-                                   const std::vector<int>& dg, bool fwd, int forceG, bool codes) {
+ChainSchedule build_chain_schedule(const ChainKnobs& kn, int n, const std::vector<int>& iaf,
+                                   const std::vector<int>& jaf, const std::vector<int>& dg, bool fwd, int forceG,
+                                   bool codes) {
   ChainSchedule S;
   S.fwd = fwd;
-  PhaseClock pc(fwd ? "fwd" : "bwd");
+  PhaseClock pc(kn.schedProf != 0, fwd ? "fwd" : "bwd");
+  const int importLat = kn.importLat;  // iterations a global value takes to reach another band (model)
   auto rb = [&](int i) { return fwd ? iaf[i] : dg[i] + 1; };
   auto re = [&](int i) { return fwd ? dg[i] : iaf[i + 1]; };
   int emax = 0;
@@ -100,10 +94,9 @@ ChainSchedule build_chain_schedule(int n, const std::vector<int>& iaf, const std
   // consecutive positions of their lane (the partial sum carried in a register, so the order of
   // the subtractions is unchanged); every row of a chain takes the chain's segment count ns.
   // Narrower rows (2D) are computed two per position (G = 2): the chain's next row takes the
-  // first one's value straight from the register (MMX_CHAIN_PAIR=0: one row per position).
+  // first one's value straight from the register (ChainKnobs::pair = 0: one row per position).
   {
-    const char* we = getenv("MMX_CHAIN_E48");
-    const bool wide = emax > 32 && emax <= kChainWideE && !(we && atoi(we) == 0);
+    const bool wide = emax > 32 && emax <= kChainWideE && kn.e48;
     S.E = emax <= 8 ? 8 : emax <= 16 ? 16 : emax <= 32 ? 32 : wide ? kChainWideE : 32;
     S.seg = emax > 32 && !wide;
   }
@@ -112,8 +105,7 @@ ChainSchedule build_chain_schedule(int n, const std::vector<int>& iaf, const std
     return S;
   }
   {
-    const char* pe = getenv("MMX_CHAIN_PAIR");
-    S.G = (!S.seg && S.E <= 16 && !(pe && atoi(pe) == 0)) ? 2 : 1;
+    S.G = (!S.seg && S.E <= 16 && kn.pair) ? 2 : 1;
     if (forceG == 1 || (forceG == 2 && !S.seg && S.E <= 16)) S.G = forceG;
   }
   const int G = S.G, E = S.E, EE = E * G;
@@ -179,7 +171,7 @@ ChainSchedule build_chain_schedule(int n, const std::vector<int>& iaf, const std
   // import reaches another band kImportLatency iterations later.  Plain skews satisfy only the
   // band's own dependencies (the band then waits for late imports); aligned skews also delay each
   // lane until its imports are due (3D: a band's chains span planes whose imports arrive at very
-  // different times).  MMX_CHAIN_ALIGN=0/1 forces one; by default the shorter modelled path wins.
+  // different times).  ChainKnobs::align 0 / > 0 forces one; by default the shorter modelled path wins.
   struct Pass1 {  // one modelled schedule: lane skews, band lengths and offsets
     std::vector<int> laneSkew, bandT;
     std::vector<long long> doneAt, offset;
@@ -211,7 +203,7 @@ ChainSchedule build_chain_schedule(int n, const std::vector<int>& iaf, const std
               if (cj >= c0 && cj < c) {
                 sk = std::max<long long>(sk, laneSkew[(size_t)b * L + (cj - c0)] + posOf[j] - p + 1);
               } else if (align && cj < c0 && doneAt[j] >= 0) {
-                sk = std::max<long long>(sk, doneAt[j] + import_latency() - off0 - p);
+                sk = std::max<long long>(sk, doneAt[j] + importLat - off0 - p);
               }
             }
           }
@@ -233,7 +225,7 @@ ChainSchedule build_chain_schedule(int n, const std::vector<int>& iaf, const std
               if (part(c, p, g, q, kb, ke) < 0) continue;
               for (int k = kb; k < ke; ++k) {
                 const int j = jaf[k];
-                if (chainOf[j] < c0 && doneAt[j] >= 0) off = std::max(off, doneAt[j] + import_latency() - (p + sk));
+                if (chainOf[j] < c0 && doneAt[j] >= 0) off = std::max(off, doneAt[j] + importLat - (p + sk));
               }
             }
       }
@@ -251,10 +243,9 @@ ChainSchedule build_chain_schedule(int n, const std::vector<int>& iaf, const std
     P.est = est;
   };
   {
-    // MMX_CHAIN_ALIGN=0/1 forces one; by default both are modelled (concurrently) and the shorter
+    // align >= 0 forces one; by default (negative) both are modelled (concurrently) and the shorter
     // critical path wins
-    const char* ae = getenv("MMX_CHAIN_ALIGN");
-    const int mode = ae ? atoi(ae) : -1;
+    const int mode = kn.align;
     Pass1 P0, P1;
     if (mode >= 0) {
       pass1(mode != 0, P0);
@@ -617,8 +608,8 @@ std::string validate_chain_schedule(const ChainSchedule& S, int n, const std::ve
   return "";
 }
 
-FactorSchedule build_factor_schedule(int n, const std::vector<int>& iaf, const std::vector<int>& jaf,
-                                     const std::vector<int>& dg) {
+FactorSchedule build_factor_schedule(const ChainKnobs& kn, int n, const std::vector<int>& iaf,
+                                     const std::vector<int>& jaf, const std::vector<int>& dg) {
   FactorSchedule F;
   for (int i = 0; i < n; ++i) {
     const int W = iaf[i + 1] - iaf[i], nl = dg[i] - iaf[i];
@@ -627,8 +618,8 @@ FactorSchedule build_factor_schedule(int n, const std::vector<int>& iaf, const s
       return F;
     }
   }
-  PhaseClock pc("factor");
-  F.geo = build_chain_schedule(n, iaf, jaf, dg, true, 1, false);  // its geometry (no stage codes)
+  PhaseClock pc(kn.schedProf != 0, "factor");
+  F.geo = build_chain_schedule(kn, n, iaf, jaf, dg, true, 1, false);  // its geometry (no stage codes)
   pc.mark("geometry");
   ChainSchedule& S = F.geo;
   if (!S.ok) {
@@ -640,8 +631,7 @@ FactorSchedule build_factor_schedule(int n, const std::vector<int>& iaf, const s
     return F;
   }
   const int L = kChainLanes;
-  const char* fr = getenv("MMX_FAC_R");
-  const int R = std::min(std::min(S.R, kFacRMax), fr ? atoi(fr) : kFacRMax);  // ring slots per lane (rows)
+  const int R = std::min(std::min(S.R, kFacRMax), kn.facR);  // ring slots per lane (rows)
   if (R != 1 && R != 2 && R != 4) {  // the ring is indexed p & (R - 1): a power of two, at most kFacRMax
     F.why = "factor ring size " + std::to_string(R) + " not in {1, 2, 4}";
     return F;
@@ -675,8 +665,7 @@ FactorSchedule build_factor_schedule(int n, const std::vector<int>& iaf, const s
   F.impNeed.assign(nslot, -1);
   F.bandImp.assign(S.nbands, 0);
   F.bandNImp.assign(S.nbands, 0);
-  const char* fri = getenv("MMX_FAC_RI");
-  const int RI = fri ? std::max(1, std::min(atoi(fri), kFacImpRows)) : kFacImpRows;  // s_dep holds kFacImpRows
+  const int RI = kn.facRI;  // (1..kFacImpRows: s_dep holds kFacImpRows)
   F.RI = RI;
   const int impBase = 1 + L * (R + 1) * kFacWU;
   struct Use {

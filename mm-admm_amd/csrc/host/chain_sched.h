@@ -28,6 +28,8 @@
 #include <utility>
 #include <vector>
 
+#include "knobs.h"
+
 namespace mmx {
 
 // an allocator whose resize() leaves ints uninitialised: the schedule's entry arrays (GBs at C4)
@@ -61,7 +63,7 @@ constexpr int kChainFwd = -2147483647;      // entry whose value is the pair's f
 constexpr int kChainSegMax = 4;      // segments of E = 32 entries a row may take (rows up to 128 entries)
 // rows of 33..48 entries (the 3D backward triangle: up to 44) take one position of a 48-entry stage
 // with 16-bit codes instead of two 32-entry segments; its LDS budget leaves a ring of 8 rows per lane
-// (chain_sweep.hip kRingWide; values farther back are imported).  MMX_CHAIN_E48=0: segments.
+// (chain_sweep.hip kRingWide; values farther back are imported).  ChainKnobs::e48 = 0: segments.
 constexpr int kChainWideE = 48;
 constexpr int kChainRingWide = 8;
 
@@ -98,9 +100,11 @@ struct ChainSchedule {
 // fwd: unit-lower sweep over the entries [iaf[i], dg[i]); !fwd: upper sweep over (dg[i], iaf[i+1]).
 // forceG: rows per position (0: automatic).  codes = false: the geometry only (bands, lanes, skews,
 // slots, ring size, ticket order) -- no entry codes, sources or import tables (the factor schedule's
-// use: it lays its own stages over the forward geometry).
-ChainSchedule build_chain_schedule(int n, const std::vector<int>& iaf, const std::vector<int>& jaf,
-                                   const std::vector<int>& dg, bool fwd, int forceG = 0, bool codes = true);
+// use: it lays its own stages over the forward geometry).  kn: the owning matrix's schedule
+// switches (knobs.h) -- the builders read no environment, so they may run on helper threads.
+ChainSchedule build_chain_schedule(const ChainKnobs& kn, int n, const std::vector<int>& iaf,
+                                   const std::vector<int>& jaf, const std::vector<int>& dg, bool fwd, int forceG = 0,
+                                   bool codes = true);
 
 // ---- the numeric ILU(0) factor on the same chain/band schedule (chain_factor.hip) ----------------
 // Row i of the factor (scaler_ILU::factor, ILU_class.cpp:300-527, IKJ order) restated target by
@@ -113,8 +117,7 @@ constexpr int kFacWF = 18;   // entries per row (2D mesh rows: <= 18)
 constexpr int kFacNL = 9;    // lower entries per row
 constexpr int kFacWU = 14;   // diagonal + upper entries per row
 constexpr int kFacNSC = 128; // 16-bit codes per row: the (e, q) update slots, then the kFacNL pivots (padded)
-constexpr int kFacImpRows = 384;  // LDS import slots (rows; 2D meshes need <= ~330 live at once)
-constexpr int kFacRMax = 4;       // ring slots per lane (rows)
+// (kFacImpRows LDS import slots and kFacRMax ring slots per lane: knobs.h, the limits of MMX_FAC_RI / MMX_FAC_R)
 // update slot of (e, q), q < min(e, kFacNL): sum over e' < e of min(e', kFacNL), plus q
 constexpr int fac_slot(int e, int q) { return (e <= kFacNL ? e * (e - 1) / 2 : kFacNL * (kFacNL - 1) / 2 + (e - kFacNL) * kFacNL) + q; }
 constexpr int kFacNUpd = fac_slot(kFacWF, 0);  // 117
@@ -140,8 +143,8 @@ struct FactorSchedule {
   long long nImports = 0;
   int maxImpSlots = 0;
 };
-FactorSchedule build_factor_schedule(int n, const std::vector<int>& iaf, const std::vector<int>& jaf,
-                                     const std::vector<int>& dg);
+FactorSchedule build_factor_schedule(const ChainKnobs& kn, int n, const std::vector<int>& iaf,
+                                     const std::vector<int>& jaf, const std::vector<int>& dg);
 // Replays the schedule: every row's update and pivot values are the reference's (ring cells of the
 // right row, written before and not overwritten; imports of the right position, delivered in time).
 std::string validate_factor_schedule(const FactorSchedule& F, int n, const std::vector<int>& iaf,

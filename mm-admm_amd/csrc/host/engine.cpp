@@ -57,6 +57,7 @@ struct EngineBase {
   virtual void regrid(double t) = 0;
   virtual void setRegrid(bool on) = 0;
   virtual void debugBlockGrad(int s, const double* z, const double* dx, int flags, double* out) = 0;
+  virtual std::string options() const = 0;
 };
 
 // Mesh::reOrientElements (src/Mesh.cpp:243-260): swap F(i,1), F(i,2) when det(E) < 0, E the
@@ -86,12 +87,27 @@ class Engine final : public EngineBase {
   static constexpr int K = D * (D + 1);
 
   Engine(int nP, const double* Xp, const double* Xc, int nF, const int32_t* F, const int32_t* mask,
-         const mmadmm_params& p, mmadmm_monitor_fn fn, void* user, Comm* comm) {
+         const mmadmm_params& p, mmadmm_monitor_fn fn, void* user, Comm* comm)
+      // element partition (a single rank owns everything); node -> incident slots in ascending
+      // global simplex id (column-major D^T order), other ranks' slots from the gathered buffer
+      : Fh_(orientedSimplices(nP, Xp, nF, F)),
+        plan_(make_partition_plan(D, nP, Xp, nF, Fh_.data(), std::max(1, p.nranks), p.nranks > 1 ? p.rank : 0,
+                                  p.partition)),
+        // every MMX_* switch, read here once (knobs.h): nothing below or after reads the environment
+        knobs_(EngineKnobs::from_env(D, (int)plan_.localSimplices.size(), std::max(1, p.nranks))) {
     dim = D;
     prm_ = p;
     nranks_ = std::max(1, p.nranks);
     rank_ = nranks_ > 1 ? p.rank : 0;
     comm_ = comm;
+    nP_ = (int)plan_.localNodes.size();
+    nF_ = (int)plan_.localSimplices.size();
+    // prox workgroups take 16 (3D quad) to 256 simplices; node kernels pad their grid to a multiple of 8 (XCD map)
+    // (k_prox_quad: 16 tets per workgroup)
+    // (at least 16 x 256: the persistent x-update sweep writes one record per workgroup, 256 per CU
+    // count of MMX_XUP_SWEEP, twice on a partition -- a larger count than that is refused here)
+    maxBlocks_ = std::max<size_t>(4096, std::max((nF_ + 15) / 16, (nP_ + 255) / 256 + 16));
+    knobs_.check_xup_sweep(maxBlocks_);
     if (nranks_ > 1 && !comm_) throw Error(MMADMM_ERR_INVALID, "partitioned engine needs a communicator");
     if (p.device >= 0) MMX_HIP(hipSetDevice(p.device));
     MMX_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
@@ -102,11 +118,7 @@ class Engine final : public EngineBase {
     }
     compMesh_ = (Xc != nullptr);
     std::vector<double> Vp(Xp, Xp + (size_t)nP * D);
-    Fh_.assign(F, F + (size_t)nF * (D + 1));
-    for (int i = 0; i < nF * (D + 1); ++i)
-      if (Fh_[i] < 0 || Fh_[i] >= nP) throw Error(MMADMM_ERR_INVALID, "simplex vertex id out of range");
     maskH_.assign(mask, mask + nP);
-    reorient_simplices(D, Vp.data(), nF, Fh_.data());
     // monitor grid (MeshInterpolator set-up), once per run on the initial vertices
     build_monitor_grid(D, Vp.data(), nP, fn, user, grid_);
     monFn_ = fn;
@@ -136,11 +148,6 @@ class Engine final : public EngineBase {
       for (int c = 0; c < D; ++c) EhatH_[r * D + c] = Ehat[r][c];
     const double d = (double)D, pp = 1.5;
     powd_ = pow(d, d * pp / 2.0);
-    // element partition (a single rank owns everything); node -> incident slots in ascending
-    // global simplex id (column-major D^T order), other ranks' slots from the gathered buffer
-    plan_ = make_partition_plan(D, nP, Vp.data(), nF, Fh_.data(), nranks_, rank_, p.partition);
-    nP_ = (int)plan_.localNodes.size();
-    nF_ = (int)plan_.localSimplices.size();
     if (nranks_ > 1) {  // vertex owners for the partitioned regrid: the rank of the lowest incident simplex
       std::vector<std::vector<int>> owned(nranks_);
       for (int v = 0; v < nP; ++v) owned[plan_.nodeOwner[v]].push_back(v);
@@ -191,24 +198,9 @@ class Engine final : public EngineBase {
     interior_.upload(interior.data(), interior.size(), st_);
     incPtr_.upload(plan_.incPtr.data(), plan_.incPtr.size(), st_);
     incOff_.upload(plan_.incSrc.data(), plan_.incSrc.size(), st_);
-    {  // the x-update terms in the slot layout (DeviceMesh::tslot): 3D (C4: prox +0.09 ms, x-update
-       // 0.36 -> 0.18 ms) and small 2D meshes, whose prox is under two rounds of the chip's resident
-       // waves, so the terms' stores cost it little (C2: 14,754 -> 15,037 it/s; C3: prox +0.034 ms,
-       // x-update -0.018 ms, 2,506 -> 2,412 it/s); MMX_TSLOT=0/1 overrides
-      const char* ts = getenv("MMX_TSLOT");
-      tslotOn_ = ts ? atoi(ts) != 0 : (D == 3 || nF_ <= kTslot2dMax);
-      const char* sp = getenv("MMX_SPIN");
-      spinWait_ = !(sp && atoi(sp) == 0);
-      const char* zx = getenv("MMX_ZX");  // 0: the step's z = D x by k_gather_z (DeviceMesh::zx)
-      zFromX_ = !(zx && atoi(zx) == 0);  // 2D and 3D, partitions too: the first pack reads zx (PackZX)
-      const char* ov = getenv("MMX_OVERLAP");  // 0: the halo exchange before the whole x-update
-      overlap_ = nranks_ > 1 && !(ov && atoi(ov) == 0);
-      const char* fp = getenv("MMX_FUSE_PRED");  // 0: k_predict runs in every step (DeviceMesh::predBar)
-      fusePred_ = !(fp && atoi(fp) == 0);
-      const char* gk = getenv("MMX_GC_SKIP");
-      gcSkip_ = !(gk && atoi(gk) == 0);
-      if (tslotOn_) tslot_.alloc(std::max<size_t>((size_t)nF_ * K, 1));
-    }
+    // the x-update terms in the slot layout (DeviceMesh::tslot): 3D and small 2D meshes, whose prox is
+    // under two rounds of the chip's resident waves, so the terms' stores cost it little
+    if (knobs_.tslot) tslot_.alloc(std::max<size_t>((size_t)nF_ * K, 1));
     {  // x-update order: nodes by their first incident (local) simplex, then id -- locality of the
        // slot gathers when the node numbering is not simplex-ordered (e.g. cell centres numbered last)
       std::vector<long long> key(nl);
@@ -219,16 +211,15 @@ class Engine final : public EngineBase {
         key[v] = k;
       }
       // an element partition orders its interior nodes (no slot of another rank) first: their
-      // x-update runs while the halo exchange is in flight (overlap_), the rest after it
+      // x-update runs while the halo exchange is in flight (EngineKnobs::overlap), the rest after it
       std::vector<int32_t> inner, bound;
       for (int v = 0; v < nl; ++v) {
         bool remote = false;
         for (int t = plan_.incPtr[v]; t < plan_.incPtr[v + 1]; ++t) remote |= plan_.incSrc[t] < 0;
-        (remote && overlap_ ? bound : inner).push_back(v);
+        (remote && knobs_.overlap ? bound : inner).push_back(v);
       }
       nInner_ = (int)inner.size();
-      const char* xo = getenv("MMX_XUP_ORDER");  // 3D default: y slabs (C4 x-update 0.174 -> 0.152 ms with the sweep)
-      const bool slabs = xo ? atoi(xo) == 1 : D == 3;
+      const bool slabs = knobs_.xupOrder;  // 3D default: y slabs
       auto order = [&](std::vector<int32_t>& ord) {
         const int n = (int)ord.size();
         if (slabs) {
@@ -252,19 +243,18 @@ class Engine final : public EngineBase {
       nodeOrder_.upload(ord.data(), std::max<size_t>(ord.size(), 1), st_);
       // the same order as records (xup_records.h): the x-update's fixed data by position, so a lane
       // reaches its z/u gathers in two dependent load phases instead of four; MMX_XUP_REC=0: the CSR
-      const char* xr = getenv("MMX_XUP_REC");
-      xupRec_ = !(xr && atoi(xr) == 0);
       XupRecords recs;
-      if (xupRec_) {
+      if (knobs_.xupRec) {
         // columns: the widest chunk a kernel of this dimension may take (a narrower one reads a prefix)
-        const int ch = std::max(D == 2 ? MMX_XU_CH2D : 8, xupChunk());
+        const int ch = std::max(D == 2 ? MMX_XU_CH2D : 8, knobs_.xupCh);
         recs = build_xup_records(nl, ord.data(), plan_.incPtr.data(), plan_.incSrc.data(), invdiag.data(), ch);
         xrec_.upload(recs.rec.data(), recs.rec.size(), st_);
         xinv_.upload(recs.invdiag.data(), recs.invdiag.size(), st_);
         xslot_.upload(recs.slot.data(), recs.slot.size(), st_);
         xslotStride_ = (int)recs.stride;
         xslotCh_ = ch;
-        const int chs = D == 2 ? MMX_XU_CH2D : xupChunk();  // the steady loop's chunk: slots past it come from inc_off
+        // the steady loop's chunk: slots past it come from inc_off
+        const int chs = D == 2 ? MMX_XU_CH2D : knobs_.xupCh;
         xupTail_ = 0;
         for (int v = 0; v < nl; ++v) xupTail_ += std::max(0, plan_.incPtr[v + 1] - plan_.incPtr[v] - chs);
       }
@@ -306,19 +296,13 @@ class Engine final : public EngineBase {
       B_.alloc(nB);
       MMX_HIP(hipMemsetAsync(B_.p, 0, nB * sizeof(double), st_));
       launch_bkinv_identity<D>(nF_, B_.p, st_);
-      wave2d_ = D == 2 && prox2d_wave_requested();
-      if (prox_double_buffered(D, wave2d_)) B2_.alloc(nB);
+      if (prox_double_buffered(D, knobs_.prox2dWave)) B2_.alloc(nB);
     }
-    // prox workgroups take 16 (3D quad) to 256 simplices; node kernels pad their grid to a multiple of 8 (XCD map)
-    // (k_prox_quad: 16 tets per workgroup)
-    // (at least 16 x 256: the persistent x-update sweep writes one record per workgroup, 256 per CU
-    // count of MMX_XUP_SWEEP, twice on a partition)
-    const size_t maxBlocks = std::max<size_t>(4096, std::max((nF_ + 15) / 16, (nP_ + 255) / 256 + 16));
-    maxBlocks_ = maxBlocks;
-    partA_.alloc(maxBlocks * kNumPartials);
-    partB_.alloc(maxBlocks * kNumPartials);
+    partA_.alloc(maxBlocks_ * kNumPartials);
+    partB_.alloc(maxBlocks_ * kNumPartials);
     redScratch_.alloc((size_t)kRedSets * kRedSplit * kNumPartials);
     red_.scratch = redScratch_.p;
+    red_.splitMin = knobs_.redSplitMin;
     resultsCap_ = 0;
     ensureResults(64);
     m_ = makeView();
@@ -360,19 +344,19 @@ class Engine final : public EngineBase {
     const double dtOverTau = prm_.dt / prm_.tau;
     // predictX (src/Mesh.cpp:649-674), then xPrev = x
     // (2D, one rank: the extrapolation of steps after the third runs inside the step's first x-update)
-    const bool fusePred = zFromX_ && fusePred_ && !wave2d_ && !(prm_.grad_use || stepsTaken_ <= 2);
+    const bool fusePred = knobs_.zx && knobs_.fusePred && !knobs_.prox2dWave && !(prm_.grad_use || stepsTaken_ <= 2);
     if (prm_.grad_use || stepsTaken_ <= 2) {
       int nb = 0;
       launch_grad_simplex<D>(m_, x_.p, gs_.p, true, partA_.p, &nb, st_);
       exchange(1);
-      launch_predict<D>(m_, 0, gs_.p, x_.p, xPrev_.p, xBar_.p, dtOverTau, st_);
+      launch_predict<D>(m_, knobs_, 0, gs_.p, x_.p, xPrev_.p, xBar_.p, dtOverTau, st_);
     } else if (!fusePred) {
-      launch_predict<D>(m_, 1, nullptr, x_.p, xPrev_.p, xBar_.p, dtOverTau, st_);
+      launch_predict<D>(m_, knobs_, 1, nullptr, x_.p, xPrev_.p, xBar_.p, dtOverTau, st_);
     }
     // x = xBar; z = D x; first step: z = D xPrev.  2D on one rank: no pass over z -- the step's first
     // x-update and first prox take z from these positions (DeviceMesh::zx; C3: -37 us per step)
     const double* zsrc = stepsTaken_ == 0 ? xPrev_.p : xBar_.p;
-    const bool zFromX = zFromX_ && !wave2d_;
+    const bool zFromX = knobs_.zx && !knobs_.prox2dWave;
     if (!stepTaken_) clearU();  // (before z: in 2D the clear takes the whole interleaved buffer)
     if (zFromX)
       m_.zx = zsrc;
@@ -419,15 +403,16 @@ class Engine final : public EngineBase {
         }
       }
       const bool firstProx = !hessComputed_;          // another kernel, another partial count
-      const bool swapB = prox_double_buffered(D, wave2d_) && hessComputed_;  // steady state B_ -> B2_, then swap
+      // steady state B_ -> B2_, then swap
+      const bool swapB = prox_double_buffered(D, knobs_.prox2dWave) && hessComputed_;
       if (hessComputed_) {  // fast + exact pair: flip the tie queue
         tiePar_ ^= 1;
         std::swap(m_.tieCount, m_.tieStale);
       }
       // a step's last prox: the next step resets z, so nothing reads the gradient cache it would leave
       // (2D; MMX_GC_SKIP=0: written as in every other prox)
-      m_.gcSkip = (D == 2 && gcSkip_ && !early && i == nIters - 1) ? 1 : 0;
-      launch_prox<D>(m_, !hessComputed_, gcacheValid_, early ? tol / 100 : 1e-3 / 100, x_.p, z_.p, uPtr(), B_.p,
+      m_.gcSkip = (D == 2 && knobs_.gcSkip && !early && i == nIters - 1) ? 1 : 0;
+      launch_prox<D>(m_, knobs_, !hessComputed_, gcacheValid_, early ? tol / 100 : 1e-3 / 100, x_.p, z_.p, uPtr(), B_.p,
                      swapB ? B2_.p : B_.p, partA_.p + (deferRed ? slice * i : 0), &nbp, st_);
       m_.zx = nullptr;  // z is in z_ from the first prox on
       if (swapB) std::swap(B_.p, B2_.p);
@@ -530,7 +515,7 @@ class Engine final : public EngineBase {
     launch_grad_simplex<D>(m_, x_.p, gs_.p, false, partA_.p, &nb, st_);
     launch_reduce_partials(partA_.p, nb, res_, st_, red_);
     exchange(1);
-    launch_euler_apply<D>(m_, gs_.p, x_.p, prm_.dt / prm_.tau, st_);
+    launch_euler_apply<D>(m_, knobs_, gs_.p, x_.p, prm_.dt / prm_.tau, st_);
     std::vector<double> rv;
     fetchResults(res_, 1, rv);
     const double* r = rv.data();
@@ -555,7 +540,7 @@ class Engine final : public EngineBase {
     MMX_HIP(hipMemcpyAsync(xn_.p, x_.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st_));
     int nb = 0, nb2 = 0;
     launch_grad_simplex<D>(m_, x_.p, gs_.p, false, partA_.p, &nb, st_);  // initial guess
-    launch_euler_apply<D>(m_, gs_.p, x_.p, dtot, st_);
+    launch_euler_apply<D>(m_, knobs_, gs_.p, x_.p, dtot, st_);
     if (!beStepTaken_) buildJacobian(dtBE);
     int nIter = 0;
     double Ih = 0.0, normPrev = INFINITY;
@@ -564,7 +549,7 @@ class Engine final : public EngineBase {
     MMX_SP(mmx_matrix_stream(jac_, &mst));
     do {
       launch_grad_simplex<D>(m_, x_.p, gs_.p, false, partA_.p, &nb, st_);
-      launch_be_residual<D>(m_, gs_.p, x_.p, xn_.p, dtot, rhs_.p, partB_.p, &nb2, st_);
+      launch_be_residual<D>(m_, knobs_, gs_.p, x_.p, xn_.p, dtot, rhs_.p, partB_.p, &nb2, st_);
       launch_reduce_partials2(partA_.p, nb, res_, partB_.p, nb2, res_ + kNumPartials, st_, red_);
       fetchResults(res_, 1, rv);
       if (rv[4] > 0) throwBad("in backward Euler");
@@ -613,13 +598,13 @@ class Engine final : public EngineBase {
       MMX_HIP(hipMemcpyAsync(xn_.p, x_.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st_));
       launch_grad_simplex<D>(m_, x_.p, gs_.p, false, partA_.p, &nb, st_);
       launch_reduce_partials(partA_.p, nb, res_, st_, red_);
-      launch_euler_apply<D>(m_, gs_.p, x_.p, dt / prm_.tau, st_);
+      launch_euler_apply<D>(m_, knobs_, gs_.p, x_.p, dt / prm_.tau, st_);
       fetchResults(res_, 1, rv);
       if (rv[4] > 0) throwBad("in backward Euler");
       if (sc) sc[0] = rv[0];
     } else if (op == 1) {
       launch_grad_simplex<D>(m_, x_.p, gs_.p, false, partA_.p, &nb, st_);
-      launch_be_residual<D>(m_, gs_.p, x_.p, xn_.p, dt / prm_.tau, rhs_.p, partB_.p, &nb2, st_);
+      launch_be_residual<D>(m_, knobs_, gs_.p, x_.p, xn_.p, dt / prm_.tau, rhs_.p, partB_.p, &nb2, st_);
       launch_reduce_partials2(partA_.p, nb, res_, partB_.p, nb2, res_ + kNumPartials, st_, red_);
       fetchResults(res_, 1, rv);
       if (rv[4] > 0) throwBad("in backward Euler");
@@ -637,7 +622,7 @@ class Engine final : public EngineBase {
       clearInvFlag();  // the FD blocks report no inversion (their energies are not checked)
       // into a scratch buffer: jval_ keeps the engine's last assembled Jacobian (mmadmm_get_jacobian)
       if (jraw_.n != jja_.n) jraw_.alloc(std::max<size_t>(jja_.n, 1));
-      launch_jac_assemble<D>(m_, jia_.p, jja_.p, dv_.p, 1.0, jraw_.p, st_, false, maxColNodes_);
+      launch_jac_assemble<D>(m_, knobs_, jia_.p, jja_.p, dv_.p, 1.0, jraw_.p, st_, false, maxColNodes_);
       MMX_HIP(hipMemcpyAsync(out, jraw_.p, jja_.n * sizeof(double), hipMemcpyDeviceToHost, st_));
       streamWait();
     } else if (op == 3) {
@@ -758,22 +743,24 @@ class Engine final : public EngineBase {
     // + the gradient cache: K doubles read at entry and written by the last BFGS iteration
     // with the slot terms (tslot, 3D) the prox also writes K doubles per simplex and the x-update
     // reads those instead of z and u
-    const double ts = tslotOn_ ? 1.0 : 0.0;
+    const double ts = knobs_.tslot ? 1.0 : 0.0;
     s->prox_bytes = nF * (4.0 * (D + 1) + 1 + 8.0 * (2 * K + K * K) * 2 + 8.0 * K * 2 + ts * 8.0 * K) +
                     nP * 8.0 * D;
     // on the records (xup_records.h) the x-update reads, by position, the record (12 B), invdiag (8 B)
     // and the steady loop's chunk of the slot table (4 CH B), and from the CSR only the offsets of the
     // slots past a node's first CH; MMX_XUP_REC=0: inc_ptr, inc_off and invdiag by node
-    const double ch = D == 2 ? MMX_XU_CH2D : xupChunk();
-    const double fixed = xupRec_ ? nP * (4.0 * kXupRecInts + 8.0 + 4.0 * ch) + 4.0 * (double)xupTail_
+    const double ch = D == 2 ? MMX_XU_CH2D : knobs_.xupCh;
+    const double fixed = knobs_.xupRec ? nP * (4.0 * kXupRecInts + 8.0 + 4.0 * ch) + 4.0 * (double)xupTail_
                                  : 4.0 * (nP + 1) + 4.0 * (D + 1) * nF + 8.0 * nP;
     s->xupdate_bytes = fixed + (16.0 - 8.0 * ts) * K * nF + 8.0 * D * nP * 2;
     s->monitor_iso = iso_ ? 1 : 0;
     s->halo_send_bytes = 8.0 * D * (double)plan_.sendOff.size();
     s->halo_recv_bytes = nranks_ > 1 ? 8.0 * D * (double)plan_.recvRows : 0.0;
     s->interior_nodes = nInner_;
-    s->overlap = overlap_ ? 1 : 0;
+    s->overlap = knobs_.overlap;
   }
+
+  std::string options() const override { return knobs_.text(); }
 
   void resetStats() override {
     resolveTimed();
@@ -832,10 +819,9 @@ class Engine final : public EngineBase {
 
   // buildMatrix (src/Mesh.cpp:262-382): the Jacobian's pattern over the D*nP unknowns, the
   // ParamIter of the reference and the symbolic ILU (sfac, done once as the reference does).
-  // MMX_SCHED_PROF=1: the first backward-Euler step's host set-up phases on stderr
-  static void profMark(const char* what, std::chrono::steady_clock::time_point& t) {
-    static const bool on = getenv("MMX_SCHED_PROF") != nullptr;
-    if (!on) return;
+  // EngineKnobs::schedProf: the first backward-Euler step's host set-up phases on stderr
+  void profMark(const char* what, std::chrono::steady_clock::time_point& t) const {
+    if (!knobs_.schedProf) return;
     const auto now = std::chrono::steady_clock::now();
     fprintf(stderr, "[sched] engine %s %.3f s\n", what, std::chrono::duration<double>(now - t).count());
     t = now;
@@ -870,8 +856,7 @@ class Engine final : public EngineBase {
     jval_.alloc(std::max<size_t>(nnz, 1));
     dv_.alloc(std::max<size_t>((size_t)nF_ * (D + 1) * D * K, 1));
     // the FD blocks' fast pass queues its near-midpoint lanes here (MMX_FDJ_FAST=0: one exact pass)
-    const char* ff = getenv("MMX_FDJ_FAST");
-    if (!(ff && atoi(ff) == 0)) fdWork_.alloc((size_t)nF_ * (D + 1) + 1);
+    if (knobs_.fdjFast) fdWork_.alloc((size_t)nF_ * (D + 1) + 1);
     xn_.alloc((size_t)n);
     rhs_.alloc((size_t)n);
     dx_.alloc((size_t)n);
@@ -891,7 +876,7 @@ class Engine final : public EngineBase {
     const double h = 10.0 * sqrt(std::numeric_limits<double>::epsilon());
     launch_fd_jac<D>(m_, Vp_.p, h, dv_.p, st_, fdWork_.p);
     clearInvFlag();
-    launch_jac_assemble<D>(m_, jia_.p, jja_.p, dv_.p, dtBE / prm_.tau, jval_.p, st_, true, maxColNodes_);
+    launch_jac_assemble<D>(m_, knobs_, jia_.p, jja_.p, dv_.p, dtBE / prm_.tau, jval_.p, st_, true, maxColNodes_);
     streamWait();
     profMark("FD Jacobian + assembly", tp);
     MMX_SP(mmx_matrix_set_values_device(jac_, jval_.p));
@@ -937,30 +922,30 @@ class Engine final : public EngineBase {
   }
 
   // the x-update of every node with the halo exchange (mode 0) before it.  On an element partition
-  // (overlap_) the interior nodes -- no slot of another rank, first in the node order -- are updated
+  // (EngineKnobs::overlap) the interior nodes -- no slot of another rank, first in the node order -- are updated
   // on the step's stream while the pack and the send/recv run on a second stream; the interface
   // nodes follow once the exchange is in.  Each node's sum is the same either way (ascending
   // global simplex id), so the positions are bit-identical; only the residual partials come as two
   // consecutive sets.  (src/MeshIntegrator.cpp:146-160: the consensus the exchange feeds.)
   void xupdateHalo(const StepScalars& sc, int* nbx, bool resid, bool useTs, const PackZX& pz) {
-    if (!overlap_) {
+    if (!knobs_.overlap) {
       exchange(0, pz);
-      launch_xupdate<D>(m_, sc, xBar_.p, z_.p, uPtr(), x_.p, partB_.p, nbx, resid, st_, useTs);
+      launch_xupdate<D>(m_, knobs_, sc, xBar_.p, z_.p, uPtr(), x_.p, partB_.p, nbx, resid, st_, useTs);
       return;
     }
     MMX_HIP(hipEventRecord(evProx_, st_));
     DeviceMesh<D> mi = m_;
     mi.xupHi = nInner_;
     int nb1 = 0, nb2 = 0;
-    launch_xupdate<D>(mi, sc, xBar_.p, z_.p, uPtr(), x_.p, partB_.p, &nb1, resid, st_, useTs);
+    launch_xupdate<D>(mi, knobs_, sc, xBar_.p, z_.p, uPtr(), x_.p, partB_.p, &nb1, resid, st_, useTs);
     MMX_HIP(hipStreamWaitEvent(st2_, evProx_, 0));
     exchange(0, pz, st2_);
     MMX_HIP(hipEventRecord(evEx_, st2_));
     MMX_HIP(hipStreamWaitEvent(st_, evEx_, 0));
     DeviceMesh<D> mb = m_;
     mb.xupLo = nInner_;
-    launch_xupdate<D>(mb, sc, xBar_.p, z_.p, uPtr(), x_.p, partB_.p + (size_t)nb1 * kNumPartials, &nb2, resid, st_,
-                      useTs);
+    launch_xupdate<D>(mb, knobs_, sc, xBar_.p, z_.p, uPtr(), x_.p, partB_.p + (size_t)nb1 * kNumPartials, &nb2, resid,
+                      st_, useTs);
     *nbx = nb1 + nb2;
   }
 
@@ -969,7 +954,7 @@ class Engine final : public EngineBase {
   // the stream's work so far has completed: an event polled in a spin (low wake-up latency; the
   // blocking stream wait costs tens of microseconds per step), or the stream wait (MMX_SPIN=0)
   void waitStream() {
-    if (!spinWait_) {
+    if (!knobs_.spin) {
       streamWait();
       return;
     }
@@ -1032,9 +1017,9 @@ class Engine final : public EngineBase {
 
   void regrid(double t) override {
     if (nranks_ > 1) {
-      const char* mode = getenv("MMX_REGRID_GATHER");  // "all": the full all-gather (round 3)
-      if (!(mode && std::string(mode) == "all") && regridNear(t)) return;
-      st_stats_.regrid_fallbacks += (mode && std::string(mode) == "all") ? 0 : 1;
+      const bool all = knobs_.regridGatherAll;  // MMX_REGRID_GATHER=all: the full all-gather (round 3)
+      if (!all && regridNear(t)) return;
+      st_stats_.regrid_fallbacks += all ? 0 : 1;
     }
     regridAll(t);
   }
@@ -1114,8 +1099,7 @@ class Engine final : public EngineBase {
     double diam = 0.0;
     for (int d = 0; d < D; ++d) diam += extMax_[d] * extMax_[d];
     diam = std::sqrt(diam);
-    const char* mg = getenv("MMX_REGRID_MARGIN");  // tests: 0 forces the fallback below
-    const double marginScale = mg ? atof(mg) : 1.0;
+    const double marginScale = knobs_.regridMargin;  // tests: 0 forces the fallback below
     for (int d = 0; d < D; ++d) {
       const std::vector<double>& g = d == 0 ? grid_.gx : d == 1 ? grid_.gy : grid_.gz;
       const int sd = (D == 3 && d < 2) ? 1 - d : d;  // the storage axis holding coordinate axis d
@@ -1207,8 +1191,7 @@ class Engine final : public EngineBase {
   // (re)build; MMX_ISO=0 keeps the full rows.
   void updateIso() {
     iso_ = false;
-    const char* e = getenv("MMX_ISO");
-    if (e && atoi(e) == 0) return;
+    if (!knobs_.iso) return;
     const long long np = (long long)(gvals_.n / (D * D));
     if (np <= 0) return;
     if ((long long)giso_.n != np) giso_.alloc(np);
@@ -1488,14 +1471,6 @@ class Engine final : public EngineBase {
     st_stats_.regrids += 1;
   }
 
-  // slots requested at once per node in the slot-term sweep: MMX_XUP_CH as the launch reads it (8, 16, 24)
-  static int xupChunk() {
-    const char* xc = getenv("MMX_XUP_CH");
-    const int c = xc ? atoi(xc) : 8;
-    return c >= 24 ? 24 : c >= 16 ? 16 : 8;
-  }
-  static constexpr int kXupEarlyDefault = 1;  // (C4 0.1421 against 0.1423 ms without, 0.1452 from the CSR)
-
   DeviceMesh<D> makeView() const {
     DeviceMesh<D> m{};
     m.nP = nP_;
@@ -1506,7 +1481,7 @@ class Engine final : public EngineBase {
     m.inc_ptr = incPtr_.p;
     m.inc_off = incOff_.p;
     m.remote = nranks_ > 1 ? remote_.p : nullptr;
-    m.tslot = tslotOn_ ? tslot_.p : nullptr;
+    m.tslot = knobs_.tslot ? tslot_.p : nullptr;
     m.gcache = gcache_.p;
     m.tieList = tieList_.p;
     m.tieCount = tieCount_.p + tiePar_;  // keep the queue's parity across a rebuilt view (regrid)
@@ -1515,30 +1490,19 @@ class Engine final : public EngineBase {
     m.nodeOrder = nodeOrder_.p;
     m.xupLo = 0;
     m.xupHi = nP_;
-    m.prox2dWave = wave2d_ ? 1 : 0;
-    {
-      const char* xs = getenv("MMX_XUP_SWEEP");  // 3D default: one workgroup per CU (profiles/r03/xupdate)
-      // 2D on the records: two workgroups per CU with the early request (C3 0.0568 against 0.0596 ms one
-      // node per lane from the CSR, C2 0.0075 against 0.0082); from the CSR one node per lane
-      m.xupSweep = xs ? std::max(0, atoi(xs)) : (D == 3 ? 1 : (xupRec_ ? 2 : 0));
-      m.xupCh = xupChunk();
-      // the records' sweep with the next node requested early (MMX_XUP_EARLY=0/1)
-      const char* xe = getenv("MMX_XUP_EARLY");
-      m.xupEarly = xe ? atoi(xe) != 0 : kXupEarlyDefault;
-    }
-    if (xupRec_) {
+    // the view's host-only ints: the engine's switches (a rebuilt view, regrid, carries the same)
+    m.prox2dWave = knobs_.prox2dWave;
+    m.xupSweep = knobs_.xupSweep;
+    m.xupCh = knobs_.xupCh;
+    m.xupEarly = knobs_.xupEarly;
+    m.forceTie = knobs_.forceTie;
+    m.monHint = knobs_.monHint;
+    if (knobs_.xupRec) {
       m.xrec = xrec_.p;
       m.xinv = xinv_.p;
       m.xslot = xslot_.p;
       m.xslotStride = xslotStride_;
       m.xslotCh = xslotCh_;
-    }
-    {
-      const char* ft = getenv("MMX_FORCE_TIE");
-      m.forceTie = ft ? atoi(ft) : 0;
-      const char* mh = getenv("MMX_MON_HINT");
-      m.monHint = mh ? atoi(mh) : 1;
-      if (m.monHint < 0 || m.monHint > 3) m.monHint = 1;
     }
     m.invdiag = invdiag_.p;
     m.Vc = compMesh_ ? Vc_.p : nullptr;
@@ -1586,7 +1550,7 @@ class Engine final : public EngineBase {
     // one rank: the reductions write their results straight into pinned host memory (no copy
     // kernel) and the step waits for them by polling an event (MMX_SPIN=0: the stream wait and a
     // device buffer); C3: the step boundary's host turnaround ~54 us ->
-    if (nranks_ == 1 && spinWait_) {
+    if (nranks_ == 1 && knobs_.spin) {
       if (resH_) MMX_HIP(hipHostFree(resH_));
       resH_ = nullptr;
       MMX_HIP(hipHostMalloc((void**)&resH_, n * sizeof(double), hipHostMallocMapped));
@@ -1631,12 +1595,25 @@ class Engine final : public EngineBase {
     return evPool_[evUsed_++];
   }
 
+  // F with every simplex positively oriented (Mesh::reOrientElements), ids checked
+  static std::vector<int32_t> orientedSimplices(int nP, const double* Xp, int nF, const int32_t* F) {
+    std::vector<int32_t> Fh(F, F + (size_t)nF * (D + 1));
+    for (int32_t v : Fh)
+      if (v < 0 || v >= nP) throw Error(MMADMM_ERR_INVALID, "simplex vertex id out of range");
+    reorient_simplices(D, Xp, nF, Fh.data());
+    return Fh;
+  }
+
+  // (the constructor's initialiser list builds these three in this order)
+  std::vector<int32_t> Fh_;
+  PartitionPlan plan_;
+  const EngineKnobs knobs_;  // fixed for the engine's life: makeView, regrid, updateIso, ... read it
   int nP_ = 0, nF_ = 0;
   mmadmm_params prm_{};
   bool compMesh_ = false;
   double w_ = 0, powd_ = 0;
   double EhatH_[9] = {0};
-  std::vector<int32_t> Fh_, maskH_;
+  std::vector<int32_t> maskH_;
   HostGrid grid_;
   // time-varying monitors: the monitor plugin, per-step regrid flag and the device set-up buffers
   mmadmm_monitor_fn monFn_ = nullptr;
@@ -1661,12 +1638,10 @@ class Engine final : public EngineBase {
   // (the first nInner_ positions of the node order), the exchange timers
   hipStream_t st2_ = nullptr;
   hipEvent_t evProx_ = nullptr, evEx_ = nullptr;
-  bool overlap_ = false;
   int nInner_ = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> exEv_;
   DevBuf<int32_t> F_, incPtr_, incOff_;
   DevBuf<double> tslot_;
-  bool tslotOn_ = false;
   DevBuf<uint8_t> sbits_, interior_;
   DevBuf<double> gcell_[3];
   DevBuf<double> giso_;  // isotropic grid: one value per point (updateIso)
@@ -1681,11 +1656,8 @@ class Engine final : public EngineBase {
   DevBuf<double> xinv_;
   int xslotStride_ = 0, xslotCh_ = 0;
   long long xupTail_ = 0;  // incident slots past their node's first chunk (stats)
-  bool xupRec_ = true, gcSkip_ = true;
-  bool wave2d_ = false;  // 2D prox through k_prox_wave<2> (double-buffered Bkinv)
   DevBuf<unsigned> tieCount_;
   int tiePar_ = 0;
-  PartitionPlan plan_;
   Comm* comm_ = nullptr;
   int rank_ = 0, nranks_ = 1;
   int resultsCap_ = 0;
@@ -1708,8 +1680,6 @@ class Engine final : public EngineBase {
   bool timing_ = false;
   std::vector<hipEvent_t> evPool_;
   size_t evUsed_ = 0;
-  bool zFromX_ = false;
-  bool fusePred_ = true;
   static constexpr bool kZUInterleaved = (D == 2) && MMX_ZU_INTER;  // = kZUInter<D> (admm_common.h)
   double* uPtr() const { return kZUInterleaved ? z_.p + D : u_.p; }
   void clearU() {  // u = 0 (2D: the whole interleaved buffer, z included)
@@ -1718,8 +1688,6 @@ class Engine final : public EngineBase {
     else
       MMX_HIP(hipMemsetAsync(u_.p, 0, u_.n * sizeof(double), st_));
   }
-  bool spinWait_ = true;         // MMX_SPIN (waitStream)
-  static constexpr int kTslot2dMax = 2 * 2048 * 64;  // 2D slot terms up to two rounds of resident prox waves
   double* res_ = nullptr;        // the reductions' results: results_.p, or the device view of resH_
   double* resH_ = nullptr;       // pinned, mapped results (one rank)
   hipEvent_t evSync_ = nullptr;
@@ -1901,6 +1869,11 @@ int mmadmm_stats_get(mmadmm_handle h, mmadmm_stats* s) {
     if (!s) throw Error(MMADMM_ERR_INVALID, "NULL stats");
     eng(h).stats(s);
   });
+}
+int mmadmm_options_get(mmadmm_handle h, char* buf, int cap) {
+  int need = 0;
+  const int rc = guarded([&] { need = mmx::knobs_detail::copy_out(eng(h).options(), buf, cap); });
+  return rc == MMADMM_OK ? need : -rc;
 }
 int mmadmm_stats_reset(mmadmm_handle h) {
   return guarded([&] { eng(h).resetStats(); });

@@ -29,12 +29,12 @@ namespace {
 
 // MatrixStruc (lib/LASolver/MatrixIter.cpp:88-257): per-row column lists; pack() sorts each row
 // ascending and removes duplicates; the diagonal is present unless no_diag.
-// MMX_SCHED_PROF=1: phase times of the host set-up on stderr
+// ChainKnobs::schedProf: phase times of the host set-up on stderr
 struct PhaseTimer {
   bool on;
   const char* who;
   std::chrono::steady_clock::time_point t;
-  explicit PhaseTimer(const char* w) : on(getenv("MMX_SCHED_PROF") != nullptr), who(w), t(std::chrono::steady_clock::now()) {}
+  PhaseTimer(bool on_, const char* w) : on(on_), who(w), t(std::chrono::steady_clock::now()) {}
   void mark(const char* what) {
     if (!on) return;
     const auto now = std::chrono::steady_clock::now();
@@ -199,15 +199,6 @@ void symbolic_ilu(int n, const std::vector<int>& ia, const std::vector<int>& ja,
 
 namespace {
 
-// SpMV kernel: 2 = k_spmv2 (default), 1 = k_spmv (MMX_SPMV=1; kept for A/B measurements)
-int spmv_version() {
-  static int v = [] {
-    const char* e = getenv("MMX_SPMV");
-    return (e && atoi(e) == 1) ? 1 : 2;
-  }();
-  return v;
-}
-
 // userOrder: a user ordering vector is set, which overrides ParamIter.order (get_lorder,
 // lib/LASolver/MatrixIter.cpp:491-518)
 void check_params(const mmx_param_iter& p, bool userOrder = false) {
@@ -241,6 +232,9 @@ struct Timer {
 }  // namespace
 
 struct SparseMatrix {
+  // the MMX_* switches as they stood when the matrix was created (knobs.h): sfac, the solves and
+  // the launchers read these, never the environment
+  const MatrixKnobs knobs = MatrixKnobs::from_env();
   int device = 0;
   hipStream_t st = nullptr;
   int n = 0;
@@ -266,7 +260,7 @@ struct SparseMatrix {
   DevBuf<uint64_t> d_gy, d_gx;
   unsigned epoch = 0, fepoch = 0;
   // chain/band-scheduled sweeps (host/chain_sched.h); level-scheduled when a schedule is not
-  // possible or MMX_SWEEP=level (rows wider than 32 entries: segmented schedule, chain_sched.h)
+  // possible or with MatrixKnobs::sweepLevel (rows wider than 32 entries: segmented schedule, chain_sched.h)
   struct ChainDir {
     int E = 0;
     long long nent = 0, nslot = 0;
@@ -279,7 +273,7 @@ struct SparseMatrix {
   ChainDir chf, chb;
   bool useChain = false;
   // the numeric factor on the forward chain/band schedule (chain_factor.hip, 2D rows); the
-  // level schedule otherwise or with MMX_FACTOR=level
+  // level schedule otherwise or with MatrixKnobs::factor = level
   struct FactorDir {
     DevBuf<int> bandSlot, bandT, laneLen, laneSkew, bandOrder, bandImp, bandNImp, impPos, impCnt, impSlot, impWait,
         impNeed, meta, rowStart, vsrc;
@@ -291,8 +285,8 @@ struct SparseMatrix {
   bool useChainFactor = false;
   bool facWave = false;     // k_ilu_factor_wave (one wavefront per row) over d_permw
   DevBuf<int> d_permw;
-  DevBuf<uint64_t> d_gF;    // the wave factor's granules (MMX_FACTOR_GRAN=0: flags + drained stores)
-  DevBuf<unsigned long long> d_cprof;  // MMX_CHAIN_PROF: 2 x 512 counters (forward, backward)
+  DevBuf<uint64_t> d_gF;    // the wave factor's granules (MatrixKnobs::factorGran; else flags + drained stores)
+  DevBuf<unsigned long long> d_cprof;  // MatrixKnobs::chainProf: 2 x 512 counters (forward, backward)
   // numeric factor cache: the ILU of unchanged values is the same, so a solve re-factors only
   // after set_values / sfac (the reference re-factors in every solve, MatrixIter.cpp:684)
   long long valVersion = 0, factVersion = -1;
@@ -416,14 +410,10 @@ struct SparseMatrix {
   // the stream's work so far has completed, waited for by polling an event: the per-iteration
   // convergence readback of CG-STAB waits in a spin, not in the blocking stream wait, whose wake-up
   // latency varied by milliseconds on a loaded host (a backward-Euler step 24-34 ms over runs of the
-  // same kernels); MMX_SPIN=0: the stream wait
+  // same kernels); MatrixKnobs::spin = 0: the stream wait
   hipEvent_t evSpin = nullptr;
   void spin_sync() {
-    static const bool spin = [] {
-      const char* e = getenv("MMX_SPIN");
-      return !(e && atoi(e) == 0);
-    }();
-    if (!spin) {
+    if (!knobs.spin) {
       MMX_HIP(hipStreamSynchronize(st));
       return;
     }
@@ -439,7 +429,8 @@ struct SparseMatrix {
 
   void sfac(const mmx_param_iter& p) {
     check_params(p, haveUser);
-    PhaseTimer pt("sfac");
+    PhaseTimer pt(knobs.sched.schedProf != 0, "sfac");
+    enum { kFactorAuto = 0, kFactorLevel, kFactorGlobal, kFactorWave };  // MatrixKnobs::factor
     // with a user ordering: B = P A P^T with sorted rows and the gather map of its values; from here
     // on everything is built on (pia, pja) -- B's pattern, or A's own in natural order
     const bool ord = haveUser;
@@ -476,10 +467,9 @@ struct SparseMatrix {
     for (int i = 0; i < n; ++i) dg[i] = iaf[i] + dgRel[i];
     // the sweep and factor schedules (the bulk of the host set-up: DESIGN.md §7b) depend only on the
     // factor's pattern: built on helper threads while this one prepares the rest
-    const char* smode = getenv("MMX_SWEEP");
-    const bool tryChain = !(smode && std::strcmp(smode, "level") == 0);
-    const char* fmode = getenv("MMX_FACTOR");
-    const bool tryChainFactor = !(fmode && (std::strcmp(fmode, "level") == 0 || std::strcmp(fmode, "global") == 0));
+    const bool tryChain = !knobs.sweepLevel;
+    const int fmode = knobs.factor;
+    const bool tryChainFactor = fmode != kFactorLevel && fmode != kFactorGlobal;
     ChainSchedule Fs, Bs;
     FactorSchedule FS;
     std::vector<std::thread> helpers;
@@ -497,24 +487,23 @@ struct SparseMatrix {
     };
     // each sweep schedule is uploaded by its helper as soon as it is built (2D: under the factor
     // schedule, the longest of the three); a failed one leaves useChain off below
-    const char* pe = getenv("MMX_CHAIN_PROF");
-    if (tryChain && pe && atoi(pe) && !d_cprof.p) {
+    if (tryChain && knobs.chainProf && !d_cprof.p) {
       d_cprof.alloc(1024);
       MMX_HIP(hipMemsetAsync(d_cprof.p, 0, 1024 * sizeof(unsigned long long), st));
     }
     bool upF = false, upB = false;
     if (tryChain) {
       helper(0, [&] {
-        Bs = build_chain_schedule(n, iaf, jaf, dg, false);
+        Bs = build_chain_schedule(knobs.sched, n, iaf, jaf, dg, false);
         if (Bs.ok) {
           upload_chain(Bs, chb);
           upB = true;
           release(Bs);
         }
       });
-      if (tryChainFactor) helper(1, [&] { FS = build_factor_schedule(n, iaf, jaf, dg); });
+      if (tryChainFactor) helper(1, [&] { FS = build_factor_schedule(knobs.sched, n, iaf, jaf, dg); });
       helper(2, [&] {
-        Fs = build_chain_schedule(n, iaf, jaf, dg, true);
+        Fs = build_chain_schedule(knobs.sched, n, iaf, jaf, dg, true);
         if (Fs.ok) {
           upload_chain(Fs, chf);
           upF = true;
@@ -558,8 +547,7 @@ struct SparseMatrix {
       }
       for (int i = 0; i < n; ++i) rowTot[i + 1] += rowTot[i];
       const long long tot = rowTot[n];
-      const char* fm = getenv("MMX_FACTOR");
-      facLds = maxW <= kFacW && tot < (1ll << 31) && !(fm && std::strcmp(fm, "global") == 0);
+      facLds = maxW <= kFacW && tot < (1ll << 31) && fmode != kFactorGlobal;
       DevBuf<long long> d_rowTot;
       d_rowTot.upload(rowTot.data(), rowTot.size(), st);
       d_piv.alloc(std::max<size_t>(jaf.size(), 1));
@@ -629,16 +617,15 @@ struct SparseMatrix {
       // default where the rows fit its layout (2D): bit-identical to the level schedule and
       // 12.3 ms against 25.0 ms at n = 2 M (profiles/r03/chain_factor/);
       // MMX_FACTOR=level (or global) keeps the level-scheduled factor
-      const char* fm = fmode;
       if (useChain && tryChainFactor && jaf.size() < ((size_t)1 << 27)) {  // (32-bit granule byte offsets)
-        if (FS.ok && !(fm && std::strcmp(fm, "wave") == 0)) {
+        if (FS.ok && fmode != kFactorWave) {
           upload_factor(FS, dg);
           useChainFactor = true;
         }
       }
       // otherwise one wavefront per row (3D rows: 45 ms -> see DESIGN.md §7) where the rows fit it;
       // MMX_FACTOR=level keeps the level-scheduled lane-per-row factor
-      if (!useChainFactor && facLds && !(fm && (std::strcmp(fm, "level") == 0 || std::strcmp(fm, "global") == 0))) {
+      if (!useChainFactor && facLds && fmode != kFactorLevel && fmode != kFactorGlobal) {
         // the row image is scattered by all lanes at once: no two entries of A onto one factor slot
         // (rows in parallel; a row's amap is increasing when its columns are, else sorted here)
         int fitsAll = 1;
@@ -669,8 +656,7 @@ struct SparseMatrix {
           // MMX_FACTOR_GRAN=1: publish through tagged granules instead of drained stores + a flag
           // (measured: C4 factor 11.1 -> 12.0 ms, 2D 13.4 -> 13.5 ms; profiles/r05/experiments/
           // lasolver3d/factor_gran_ab.jsonl)
-          const char* fg = getenv("MMX_FACTOR_GRAN");
-          if (fg && atoi(fg) == 1) {
+          if (knobs.factorGran) {
             d_gF.alloc(2 * jaf.size());
             MMX_HIP(hipMemsetAsync(d_gF.p, 0, d_gF.n * sizeof(uint64_t), st));
           } else {
@@ -723,10 +709,6 @@ struct SparseMatrix {
     obj = T();
   }
 
-  static int chain_trim() {
-    const char* e = getenv("MMX_CHAIN_TRIM");
-    return (e && atoi(e) == 0) ? 0 : 1;
-  }
   void upload_chain(const ChainSchedule& S, ChainDir& c) {
     auto up = [&](DevBuf<int>& d, const auto& h) {
       if (h.empty()) {
@@ -797,12 +779,11 @@ struct SparseMatrix {
     c.nslot = (long long)S.dsrc.size();
     c.val.alloc(std::max<long long>(c.nent, 1));
     c.dval.alloc(std::max<long long>(c.nslot, 1));
-    const char* pe = getenv("MMX_CHAIN_PROF");
     c.args = ChainArgs{c.bandSlot.p, c.bandT.p, c.bandImp.p, c.bandNImp.p, c.laneStart.p, c.laneLen.p, c.laneSkew.p,
                        c.laneNs.p, c.bandE.p, c.val.p, codePtr, c.dval.p, c.impRow.p, c.impSlot.p, c.impWait.p, c.impNeed.p,
                        c.bandOrder.p, S.nbands, S.R, S.RI, S.seg ? 1 : 0, S.G,
-                       d_cprof.p ? d_cprof.p + (S.fwd ? 0 : 512) : nullptr, (pe && atoi(pe) >= 2) ? 1 : 0,
-                       chain_trim()};
+                       d_cprof.p ? d_cprof.p + (S.fwd ? 0 : 512) : nullptr, knobs.chainProf >= 2 ? 1 : 0,
+                       knobs.chainTrim};
   }
 
   void upload_factor(const FactorSchedule& F, const std::vector<int>& dg) {
@@ -896,13 +877,13 @@ struct SparseMatrix {
       launch_chain_fill((long long)chfac.vsrc.n, chfac.vsrc.p, chfac.af0.p, chfac.val.p, 0.0, st);
       launch_chain_factor(chfac.args, d_af.p, chfac.gU.p, fepoch, tickets(), errw(), st);
     } else if (facWave) {
-      launch_ilu_factor_wave(f_ia, f_a, d_amap.p, d_iaf.p, d_dg.p, d_piv.p, d_jaf.p, d_toff.p, d_tgt.p, d_permw.p, n,
-                             d_af.p, d_flags.p, d_gF.n ? d_gF.p : nullptr, fepoch, tickets(), errw(), st);
+      launch_ilu_factor_wave(knobs, f_ia, f_a, d_amap.p, d_iaf.p, d_dg.p, d_piv.p, d_jaf.p, d_toff.p, d_tgt.p, d_permw.p,
+                             n, d_af.p, d_flags.p, d_gF.n ? d_gF.p : nullptr, fepoch, tickets(), errw(), st);
     } else if (facLds)
-      launch_ilu_factor_lds(f_ia, f_a, d_amap.p, d_iaf.p, d_jaf.p, d_dg.p, d_piv.p, d_toff.p, d_tgt.p, d_permf.p, nchf,
-                            d_af.p, d_flags.p, fepoch, tickets(), errw(), st);
+      launch_ilu_factor_lds(knobs, f_ia, f_a, d_amap.p, d_iaf.p, d_jaf.p, d_dg.p, d_piv.p, d_toff.p, d_tgt.p, d_permf.p,
+                            nchf, d_af.p, d_flags.p, fepoch, tickets(), errw(), st);
     else
-      launch_ilu_factor(f_ia, f_ja, f_a, d_amap.p, d_iaf.p, d_jaf.p, d_dg.p, d_piv.p, d_permf.p, nchf, d_af.p,
+      launch_ilu_factor(knobs, f_ia, f_ja, f_a, d_amap.p, d_iaf.p, d_jaf.p, d_dg.p, d_piv.p, d_permf.p, nchf, d_af.p,
                         d_flags.p, fepoch, tickets(), errw(), st);
     if (useChain) {  // the sweeps read the factor's entries in schedule order
       launch_chain_fill(chf.nent, chf.src.p, d_af.p, chf.val.p, 0.0, st);
@@ -945,14 +926,13 @@ struct SparseMatrix {
       launch_chain_sweep(true, pro, chf.E, chf.args, src, p, d_res.p, d_avbar.p, d_sc.p, nullptr, d_gy.p, nullptr, ey,
                          tk, errw(), st);
     else
-      launch_sweep(true, pro, d_iaf.p, d_jaf.p, d_dg.p, d_af.p, d_permf.p, nchf, src, p, d_res.p, d_avbar.p, d_sc.p,
-                   nullptr, d_gy.p, nullptr, ey, tk, errw(), st);
+      launch_sweep(knobs, true, pro, d_iaf.p, d_jaf.p, d_dg.p, d_af.p, d_permf.p, nchf, src, p, d_res.p, d_avbar.p,
+                   d_sc.p, nullptr, d_gy.p, nullptr, ey, tk, errw(), st);
     const unsigned ex = next_epoch();
     // the backward sweep's result taken from the granules it publishes for every row anyway, by a
     // vector pass after it: one store less per row on the compute wave (n = 2 M: sweeps 2.14-2.17 ->
-    // 2.02 ms, solve 47.7-48.2 -> 45.8-46.0 ms; MMX_BWD_GRAN=0: the sweep stores it)
-    const char* bg = getenv("MMX_BWD_GRAN");
-    const bool fromGran = !(bg && atoi(bg) == 0);
+    // 2.02 ms, solve 47.7-48.2 -> 45.8-46.0 ms; MatrixKnobs::bwdGran = 0: the sweep stores it)
+    const bool fromGran = knobs.bwdGran != 0;
     if (useChain) {
       launch_chain_sweep(false, 0, chb.E, chb.args, nullptr, nullptr, nullptr, nullptr, nullptr, d_gy.p, d_gx.p,
                          fromGran ? nullptr : out, ex, tk + 1, errw(), st);
@@ -961,8 +941,8 @@ struct SparseMatrix {
       else if (fromGran)
         launch_gran_extract(n, d_gx.p, out, st);
     } else
-      launch_sweep(false, 0, d_iaf.p, d_jaf.p, d_dg.p, d_af.p, d_permb.p, nchb, nullptr, nullptr, nullptr, nullptr,
-                   nullptr, d_gy.p, d_gx.p, out, ex, tk + 1, errw(), st);
+      launch_sweep(knobs, false, 0, d_iaf.p, d_jaf.p, d_dg.p, d_af.p, d_permb.p, nchb, nullptr, nullptr, nullptr,
+                   nullptr, nullptr, d_gy.p, d_gx.p, out, ex, tk + 1, errw(), st);
     if (ordered && !(useChain && fromGran)) launch_order_exit(n, d_inv.p, d_pv.p, userOut, st);
     MMX_HIP(hipGetLastError());
     const float ms = end(1);
@@ -975,7 +955,7 @@ struct SparseMatrix {
 
   void spmv(int epi, const double* x, double* y, const double* e1) {
     begin(0);
-    if (spmv_version() == 1)
+    if (knobs.spmv == 1)
       launch_spmv(epi, nblk, d_rowblk.p, d_ia.p, d_ja.p, d_a.p, x, y, e1, d_part.p, st);
     else
       launch_spmv2(epi, nblk, d_desc.p, d_ia.p, d_ja.p, d_a.p, x, y, e1, d_part.p, st);
@@ -1118,10 +1098,9 @@ struct SparseMatrix {
     const double* tol = tolSet ? d_tol.p : nullptr;
     // the forward sweeps' CG-STAB prologues (p and s updates) as vector passes before them, so the
     // sweeps read one operand and store nothing but their results (n = 2 M: average sweep 2.61 ->
-    // 2.16-2.20 ms, solve 55.6 -> 48.5-49.0 ms; MMX_CGS_UNFUSE=0: fused into the forward sweeps)
-    const char* uf = getenv("MMX_CGS_UNFUSE");
+    // 2.16-2.20 ms, solve 55.6 -> 48.5-49.0 ms; MatrixKnobs::cgsUnfuse = 0: fused into the forward sweeps)
     // (with an ordering always: the fused prologues index the rows naturally)
-    const bool unfuse = ordered || !(uf && atoi(uf) == 0);
+    const bool unfuse = ordered || knobs.cgsUnfuse;
     int conv = 0, it = 0;
     for (int iter = 1; iter <= p.nitmax; ++iter) {
       ++it;
@@ -1635,10 +1614,20 @@ int mmx_matrix_stats_get(mmx_matrix m, mmx_sparse_stats* out) {
   });
 }
 
+int mmx_matrix_options_get(mmx_matrix m, char* buf, int cap) {
+  int need = 0;
+  const int rc = guarded([&] {
+    MMX_M(m);
+    need = mmx::knobs_detail::copy_out(M.knobs.text(), buf, cap);
+  });
+  return rc == MMADMM_OK ? need : -rc;
+}
+
 int mmx_matrix_chain_prof(mmx_matrix m, unsigned long long* out, int reset) {
   return guarded([&] {
     MMX_M(m);
-    if (!M.d_cprof.p) throw Error(MMADMM_ERR_INVALID, "chain profiling off (set MMX_CHAIN_PROF=1 before sfac)");
+    if (!M.d_cprof.p)
+      throw Error(MMADMM_ERR_INVALID, "chain profiling off (set MMX_CHAIN_PROF=1 before the matrix is created)");
     if (out)
       MMX_HIP(hipMemcpyAsync(out, M.d_cprof.p, 1024 * sizeof(unsigned long long), hipMemcpyDeviceToHost, M.st));
     if (reset) MMX_HIP(hipMemsetAsync(M.d_cprof.p, 0, 1024 * sizeof(unsigned long long), M.st));
@@ -1675,7 +1664,8 @@ int mmx_sweep_schedule_info(int n, const int32_t* ia, const int32_t* ja, int lev
     mmx::symbolic_ilu(n, via, vja, level, fia, fja, dgRel);
     std::vector<int> dg(n);
     for (int i = 0; i < n; ++i) dg[i] = fia[i] + dgRel[i];
-    const mmx::ChainSchedule S = mmx::build_chain_schedule(n, fia, fja, dg, fwd != 0);
+    // (no matrix: the schedule switches as the environment has them now)
+    const mmx::ChainSchedule S = mmx::build_chain_schedule(mmx::ChainKnobs::from_env(), n, fia, fja, dg, fwd != 0);
     int nlev = 0;
     {
       std::vector<int> lev(n, 0);
@@ -1703,7 +1693,7 @@ int mmx_factor_schedule_info(int n, const int32_t* ia, const int32_t* ja, int le
     mmx::symbolic_ilu(n, via, vja, level, fia, fja, dgRel);
     std::vector<int> dg(n);
     for (int i = 0; i < n; ++i) dg[i] = fia[i] + dgRel[i];
-    const mmx::FactorSchedule F = mmx::build_factor_schedule(n, fia, fja, dg);
+    const mmx::FactorSchedule F = mmx::build_factor_schedule(mmx::ChainKnobs::from_env(), n, fia, fja, dg);
     int nlev = 0;
     {
       std::vector<int> lev(n, 0);

@@ -168,23 +168,12 @@ __device__ __forceinline__ void write_tslot(const DeviceMesh<D>& m, int s, const
   for (int i = 0; i < K; ++i) ts[i] = m.w * (m.w * (z[i] - u[i]));
 }
 
-// ---- host side (inline, not static: one MMX_XCD_MAP read per process, not one per object) ----
+// ---- host side ----
 inline int nblk(int n) { return (n + kBlock - 1) / kBlock; }
 // node kernels: grid padded to a multiple of the 8 XCDs, logical blocks dealt in contiguous runs
 // per XCD (blocks b and b+8 share an XCD, MI355X_MICROARCH.md §Workgroup dispatch), so the z/u
-// lines a run of nodes shares stay in one L2.  MMX_XCD_MAP=0 restores the identity mapping.
-inline int xcd_map() {
-  static int v = [] {
-    const char* e = getenv("MMX_XCD_MAP");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-inline int nblk_xcd(int n) { return xcd_map() ? (nblk(n) + 7) / 8 * 8 : nblk(n); }
-inline bool env_is(const char* name, const char* value) {  // the switch `name` is set to `value` (read now)
-  const char* e = getenv(name);
-  return e && std::string(e) == value;
-}
+// lines a run of nodes shares stay in one L2.  xcdMap (EngineKnobs::xcdMap) = 0: the identity mapping.
+inline int nblk_xcd(int n, int xcdMap) { return xcdMap ? (nblk(n) + 7) / 8 * 8 : nblk(n); }
 
 // The monitor path of a launch as a compile-time constant, f(std::integral_constant<int, ISO>) with gridOf's
 // ISO -- 3D: 1 with an isotropic grid (m.giso), else 0; 2D: -1: a dimension instantiates only what it launches

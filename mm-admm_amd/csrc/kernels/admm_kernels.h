@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../host/knobs.h"
 #include "layout.h"
 
 namespace mmx {
@@ -78,7 +79,7 @@ struct DeviceMesh {
   double Ehat[9];
   double powd, w;
   int compMesh;
-  int prox2dWave;  // 2D steady-state prox through k_prox_wave<2> (engine set-up: MMX_PROX2D=wave)
+  int prox2dWave;  // 2D steady-state prox through k_prox_wave<2> (EngineKnobs::prox2dWave)
 };
 
 struct StepScalars {
@@ -90,11 +91,13 @@ void launch_gather_z(const DeviceMesh<D>& m, const double* x, double* z, hipStre
 template <int D>
 void launch_grad_simplex(const DeviceMesh<D>& m, const double* x, double* gs, bool zeroFixed,
                          double* partials, int* nblocks, hipStream_t st);
+// (a launcher whose choice of kernel or grid depends on a run-time switch takes the engine's
+// EngineKnobs, host/knobs.h: no launcher reads the environment)
 template <int D>
-void launch_predict(const DeviceMesh<D>& m, int mode, const double* gs, double* x, double* xPrev,
+void launch_predict(const DeviceMesh<D>& m, const EngineKnobs& k, int mode, const double* gs, double* x, double* xPrev,
                     double* xBar, double dt_over_tau, hipStream_t st);
 template <int D>
-void launch_xupdate(const DeviceMesh<D>& m, const StepScalars& sc, const double* xBar,
+void launch_xupdate(const DeviceMesh<D>& m, const EngineKnobs& k, const StepScalars& sc, const double* xBar,
                     const double* z, const double* u, double* x, double* partials, int* nblocks,
                     bool resid, hipStream_t st, bool useTslot = false);
 // useCache: z is unchanged since the previous prox, whose last blockGrad left the unregularised
@@ -112,26 +115,25 @@ void launch_bkinv_identity(int nF, double* B, hipStream_t st);
 // the steady-state prox reads one Bkinv buffer and writes the other (the engine swaps them):
 // always in 3D (k_prox_wave), in 2D with k_prox_wave<2> (DeviceMesh::prox2dWave)
 bool prox_double_buffered(int D, bool wave2d);
-bool prox2d_wave_requested();  // MMX_PROX2D=wave
 template <int D>
-void launch_prox(const DeviceMesh<D>& m, bool first, bool useCache, double tol, const double* x, double* z,
-                 double* u, const double* Bin, double* Bout, double* partials, int* nblocks, hipStream_t st);
+void launch_prox(const DeviceMesh<D>& m, const EngineKnobs& k, bool first, bool useCache, double tol, const double* x,
+                 double* z, double* u, const double* Bin, double* Bout, double* partials, int* nblocks, hipStream_t st);
 template <int D>
 void launch_energy(const DeviceMesh<D>& m, const double* x, double* partials, int* nblocks,
                    hipStream_t st);
 template <int D>
-void launch_euler_apply(const DeviceMesh<D>& m, const double* gs, double* x, double dt_over_tau,
+void launch_euler_apply(const DeviceMesh<D>& m, const EngineKnobs& k, const double* gs, double* x, double dt_over_tau,
                         hipStream_t st);
 // Work space of the split reductions: each set of partials is cut into kRedSplit fixed ranges, one
 // workgroup each, and a second launch combines the kRedSplit range results of each set in range
 // order -- a fixed shape, so the sums are deterministic.  scratch: kRedSets x kRedSplit x
-// kNumPartials doubles.  A null RedWork (or a set of fewer than kRedSplitMin partials) takes one
+// kNumPartials doubles.  A null RedWork (or a set of fewer than splitMin partials) takes one
 // workgroup per set.
 constexpr int kRedSplit = 32;
-constexpr int kRedSplitMin = 4096;
 constexpr int kRedSets = 66;  // kDeferMax (engine.cpp) + 2
 struct RedWork {
   double* scratch = nullptr;
+  int splitMin = kRedSplitMin;  // EngineKnobs::redSplitMin (tests force the split form on small meshes)
 };
 void launch_reduce_partials(const double* partials, int nblocks, double* out, hipStream_t st, const RedWork& w = {});
 // a step's reductions at once: results[i*2*kNumPartials ..] from partA slice i (i < n), the x-update's
@@ -169,13 +171,13 @@ void launch_fd_jac(const DeviceMesh<D>& m, const double* Vp, double h, double* d
 // (finish = false: the sums alone, before the scaling and the identity).
 template <int D>
 // maxColNodes: the widest row's column nodes (at most 64: one wavefront per node, else one lane per row)
-void launch_jac_assemble(const DeviceMesh<D>& m, const int* ia, const int* ja, const double* dv,
+void launch_jac_assemble(const DeviceMesh<D>& m, const EngineKnobs& k, const int* ia, const int* ja, const double* dv,
                          double dt_over_tau, double* a, hipStream_t st, bool finish = true, int maxColNodes = 65);
 // Newton residual F = (dt/tau) grad + (x - xn) with grad the INTERIOR-only scatter of gs
 // (eulerStepMod, src/Mesh.cpp:532-579); rhs = -F; partial record v[0] = sum |F_i|.
 template <int D>
-void launch_be_residual(const DeviceMesh<D>& m, const double* gs, const double* x, const double* xn,
-                        double dt_over_tau, double* rhs, double* partials, int* nblocks, hipStream_t st);
+void launch_be_residual(const DeviceMesh<D>& m, const EngineKnobs& k, const double* gs, const double* x,
+                        const double* xn, double dt_over_tau, double* rhs, double* partials, int* nblocks, hipStream_t st);
 // x += dx over n doubles
 void launch_add_inplace(int n, double* x, const double* dx, hipStream_t st);
 

@@ -305,10 +305,10 @@ void launch_fd_jac(const DeviceMesh<D>& m, const double* Vp, double h, double* d
   });
 }
 template <int D>
-void launch_jac_assemble(const DeviceMesh<D>& m, const int* ia, const int* ja, const double* dv, double dt_over_tau,
-                         double* a, hipStream_t st, bool finish, int maxColNodes) {
+void launch_jac_assemble(const DeviceMesh<D>& m, const EngineKnobs& k, const int* ia, const int* ja, const double* dv,
+                         double dt_over_tau, double* a, hipStream_t st, bool finish, int maxColNodes) {
   if (m.nP == 0) return;
-  if (env_is("MMX_JAC_ASSEMBLE", "entry"))  // the entry-outer form (read once per assembly)
+  if (k.jacAssembleEntry)  // the entry-outer form
     hipLaunchKernelGGL(k_jac_assemble<D>, dim3(nblk(m.nP * D)), dim3(kBlock), 0, st, m, ia, ja, dv, dt_over_tau,
                        finish ? 1 : 0, a);
   else if (maxColNodes <= 64)
@@ -319,18 +319,19 @@ void launch_jac_assemble(const DeviceMesh<D>& m, const int* ia, const int* ja, c
                        finish ? 1 : 0, a);
 }
 template <int D>
-void launch_be_residual(const DeviceMesh<D>& m, const double* gs, const double* x, const double* xn,
-                        double dt_over_tau, double* rhs, double* partials, int* nblocks, hipStream_t st) {
-  *nblocks = nblk_xcd(m.nP);
+void launch_be_residual(const DeviceMesh<D>& m, const EngineKnobs& k, const double* gs, const double* x,
+                        const double* xn, double dt_over_tau, double* rhs, double* partials, int* nblocks,
+                        hipStream_t st) {
+  *nblocks = nblk_xcd(m.nP, k.xcdMap);
   if (m.nP == 0) return;
   if (m.nodeOrder) {  // the node-ordered residual, then its partials in node-id order
     hipLaunchKernelGGL((k_be_residual<D, true>), dim3(*nblocks), dim3(kBlock), 0, st, m, gs, x, xn, dt_over_tau, rhs,
-                       partials, xcd_map());
-    hipLaunchKernelGGL(k_abs_partials<D>, dim3(*nblocks), dim3(kBlock), 0, st, m.nP, rhs, partials, xcd_map());
+                       partials, k.xcdMap);
+    hipLaunchKernelGGL(k_abs_partials<D>, dim3(*nblocks), dim3(kBlock), 0, st, m.nP, rhs, partials, k.xcdMap);
     return;
   }
   hipLaunchKernelGGL(k_be_residual<D>, dim3(*nblocks), dim3(kBlock), 0, st, m, gs, x, xn, dt_over_tau, rhs, partials,
-                     xcd_map());
+                     k.xcdMap);
 }
 void launch_add_inplace(int n, double* x, const double* dx, hipStream_t st) {
   if (n == 0) return;
@@ -338,10 +339,10 @@ void launch_add_inplace(int n, double* x, const double* dx, hipStream_t st) {
 }
 #define MMX_INST(D)                                                                                                 \
   template void launch_fd_jac<D>(const DeviceMesh<D>&, const double*, double, double*, hipStream_t, unsigned*);     \
-  template void launch_jac_assemble<D>(const DeviceMesh<D>&, const int*, const int*, const double*, double, double*, \
-                                       hipStream_t, bool, int);                                                     \
-  template void launch_be_residual<D>(const DeviceMesh<D>&, const double*, const double*, const double*, double,    \
-                                      double*, double*, int*, hipStream_t);
+  template void launch_jac_assemble<D>(const DeviceMesh<D>&, const EngineKnobs&, const int*, const int*,            \
+                                       const double*, double, double*, hipStream_t, bool, int);                     \
+  template void launch_be_residual<D>(const DeviceMesh<D>&, const EngineKnobs&, const double*, const double*,       \
+                                      const double*, double, double*, double*, int*, hipStream_t);
 MMX_INST(2)
 MMX_INST(3)
 }  // namespace mmx

@@ -941,32 +941,15 @@ void launch_bkinv_identity(int nF, double* B, hipStream_t st) {
 }
 template void launch_bkinv_identity<2>(int, double*, hipStream_t);
 template void launch_bkinv_identity<3>(int, double*, hipStream_t);
-// reuse of the previous prox's last gradient at the prox entry (MMX_GRAD_CACHE=0 disables)
-static int cache_enabled() {
-  static int v = [] {
-    const char* e = getenv("MMX_GRAD_CACHE");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-// workgroup size of the steady-state 2D prox (MMX_PROX_BLOCK = 64 | 128 | 256 overrides)
-static int prox_block() {
-  static int b = [] {
-    const char* e = getenv("MMX_PROX_BLOCK");
-    const int v = e ? atoi(e) : 0;
-    return (v == 64 || v == 128 || v == 256) ? v : kProxBlock;
-  }();
-  return b;
-}
-
+// The engine's switches as launch_prox takes them (EngineKnobs, fixed when the engine is created):
+// gradCache: the prox entry reuses the previous prox's last gradient; proxBlock: the steady-state 2D
+// prox's workgroup (64, 128 or 256).
 // 3D steady-state prox kernel: k_prox_wave (one lane per tet, default: C4 2.77 ms) or k_prox_quad
-// (four lanes per tet, MMX_PROX3D=quad: bit-identical, C4 3.92 ms -- DESIGN.md §3).  Read at every
-// launch, so a test can switch kernels between steps.
-// 2D steady-state prox kernel: k_prox_lds (default) or k_prox_wave<2> (DeviceMesh::prox2dWave, set
-// from MMX_PROX2D=wave when the engine is built: one wave per workgroup, every Bkinv row held in
-// LDS, double-buffered, rows written as the update forms them; measured slower)
+// (four lanes per tet, prox3dQuad: bit-identical, C4 3.92 ms -- DESIGN.md §3).
+// 2D steady-state prox kernel: k_prox_lds (default) or k_prox_wave<2> (DeviceMesh::prox2dWave, from
+// EngineKnobs::prox2dWave: one wave per workgroup, every Bkinv row held in LDS, double-buffered,
+// rows written as the update forms them; measured slower)
 bool prox_double_buffered(int D, bool wave2d) { return D == 3 || wave2d; }
-bool prox2d_wave_requested() { return env_is("MMX_PROX2D", "wave"); }
 #ifdef MMX_WAVE_PROF
 static unsigned long long* g_wprofHost = nullptr;
 static size_t g_wprofN = 0;
@@ -980,12 +963,13 @@ static void wprof_arm(int nblocks) {
 }
 #endif
 template <int D>
-void launch_prox(const DeviceMesh<D>& m, bool first, bool useCache, double tol, const double* x, double* z, double* u,
-                 const double* Bin, double* Bout, double* partials, int* nblocks, hipStream_t st) {
+void launch_prox(const DeviceMesh<D>& m, const EngineKnobs& k, bool first, bool useCache, double tol, const double* x,
+                 double* z, double* u, const double* Bin, double* Bout, double* partials, int* nblocks,
+                 hipStream_t st) {
 #ifdef MMX_WAVE_PROF
   if (D == 3 && !first) wprof_arm((m.nF + 63) / 64);
 #endif
-  const int uc = (useCache && cache_enabled()) ? 1 : 0;
+  const int uc = (useCache && k.gradCache) ? 1 : 0;
   *nblocks = nblk(m.nF);
   if (m.nF == 0) return;
   if (first) {
@@ -1003,7 +987,7 @@ void launch_prox(const DeviceMesh<D>& m, bool first, bool useCache, double tol, 
     });
   } else if constexpr (D == 2) {
     double* B = Bout;  // in place (LDS image)
-    const int bs = prox_block();
+    const int bs = k.proxBlock;
     *nblocks = (m.nF + bs - 1) / bs;
     const dim3 fg(std::min(*nblocks, kFixGrid));
     if (bs == 64) {
@@ -1019,7 +1003,7 @@ void launch_prox(const DeviceMesh<D>& m, bool first, bool useCache, double tol, 
   } else {
     *nblocks = (m.nF + 63) / 64;
     const dim3 fg(std::min(*nblocks, kFixGrid));
-    if (env_is("MMX_PROX3D", "quad")) return launch_prox_quad(m, tol, x, z, u, Bin, Bout, partials, nblocks, uc, st);
+    if (k.prox3dQuad) return launch_prox_quad(m, tol, x, z, u, Bin, Bout, partials, nblocks, uc, st);
     const dim3 wg(MMX_WAVE_PERSIST ? (std::min(*nblocks, MMX_WAVE_PERSIST) + 7) / 8 * 8 : *nblocks);
     dispatch_bool(m.compMesh != 0, [&](auto c) {
       dispatch_bool(m.giso != nullptr, [&](auto i) {
@@ -1030,10 +1014,10 @@ void launch_prox(const DeviceMesh<D>& m, bool first, bool useCache, double tol, 
     });
   }
 }
-template void launch_prox<2>(const DeviceMesh<2>&, bool, bool, double, const double*, double*, double*, const double*,
-                             double*, double*, int*, hipStream_t);
-template void launch_prox<3>(const DeviceMesh<3>&, bool, bool, double, const double*, double*, double*, const double*,
-                             double*, double*, int*, hipStream_t);
+template void launch_prox<2>(const DeviceMesh<2>&, const EngineKnobs&, bool, bool, double, const double*, double*,
+                             double*, const double*, double*, double*, int*, hipStream_t);
+template void launch_prox<3>(const DeviceMesh<3>&, const EngineKnobs&, bool, bool, double, const double*, double*,
+                             double*, const double*, double*, double*, int*, hipStream_t);
 }  // namespace mmx
 
 #ifdef MMX_WAVE_PROF

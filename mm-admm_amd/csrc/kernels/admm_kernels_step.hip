@@ -509,22 +509,18 @@ void launch_grad_simplex(const DeviceMesh<D>& m, const double* x, double* gs, bo
   });
 }
 template <int D>
-void launch_predict(const DeviceMesh<D>& m, int mode, const double* gs, double* x, double* xPrev,
-                    double* xBar, double dt_over_tau, hipStream_t st) {
+void launch_predict(const DeviceMesh<D>& m, const EngineKnobs& k, int mode, const double* gs, double* x,
+                    double* xPrev, double* xBar, double dt_over_tau, hipStream_t st) {
   if (m.nP == 0) return;
-  hipLaunchKernelGGL(k_predict<D>, dim3(nblk_xcd(m.nP)), dim3(kBlock), 0, st, m, mode, gs, x, xPrev, xBar,
-                     dt_over_tau, xcd_map());
-}
-static bool xup_sweep_resid() {
-  const char* e = getenv("MMX_XUP_SWEEP_RESID");
-  return !(e && atoi(e) == 0);
+  hipLaunchKernelGGL(k_predict<D>, dim3(nblk_xcd(m.nP, k.xcdMap)), dim3(kBlock), 0, st, m, mode, gs, x, xPrev, xBar,
+                     dt_over_tau, k.xcdMap);
 }
 template <int D>
-void launch_xupdate(const DeviceMesh<D>& m, const StepScalars& sc, const double* xBar, const double* z,
-                    const double* u, double* x, double* partials, int* nblocks, bool resid, hipStream_t st,
-                    bool useTslot) {
+void launch_xupdate(const DeviceMesh<D>& m, const EngineKnobs& k, const StepScalars& sc, const double* xBar,
+                    const double* z, const double* u, double* x, double* partials, int* nblocks, bool resid,
+                    hipStream_t st, bool useTslot) {
   const int nsub = m.xupHi - m.xupLo;  // the launch's share of the node order
-  *nblocks = nblk_xcd(nsub);
+  *nblocks = nblk_xcd(nsub, k.xcdMap);
   if (nsub <= 0) {
     *nblocks = 0;
     return;
@@ -542,7 +538,7 @@ void launch_xupdate(const DeviceMesh<D>& m, const StepScalars& sc, const double*
         dispatch_bool(rec, [&](auto rc) {
           hipLaunchKernelGGL(
               (k_xupdate<D, false, false, true, decltype(pred)::value, decltype(r)::value, decltype(rc)::value>),
-              dim3(*nblocks), dim3(kBlock), 0, st, m, sc, xBar, z, u, x, partials, xcd_map());
+              dim3(*nblocks), dim3(kBlock), 0, st, m, sc, xBar, z, u, x, partials, k.xcdMap);
         });
       });
     });
@@ -554,7 +550,7 @@ void launch_xupdate(const DeviceMesh<D>& m, const StepScalars& sc, const double*
     throw std::logic_error("launch_xupdate: predBar set for an x-update that cannot fuse predictX");
   // the sweep (persistent) form, MMX_XUP_SWEEP workgroups per CU; with the residual in the slot-term
   // form (3D): C4's last x-update of a step 0.334 -> ~0.17 ms (MMX_XUP_SWEEP_RESID=0: one node per lane)
-  const bool sweepResid = resid && ts && xup_sweep_resid();
+  const bool sweepResid = resid && ts && k.xupSweepResid;
   if (m.xupSweep > 0 && (!resid || sweepResid)) {
     const int n8 = ((nsub + kBlock - 1) / kBlock + 7) / 8 * kBlock;  // = the node order's XCD groups
     const dim3 g(256 * m.xupSweep);
@@ -592,7 +588,7 @@ void launch_xupdate(const DeviceMesh<D>& m, const StepScalars& sc, const double*
     dispatch_bool(ts, [&](auto t) {
       dispatch_bool(rec, [&](auto rc) {
         hipLaunchKernelGGL((k_xupdate<D, decltype(r)::value, decltype(t)::value, false, false, false, decltype(rc)::value>),
-                           dim3(*nblocks), dim3(kBlock), 0, st, m, sc, xBar, z, u, x, partials, xcd_map());
+                           dim3(*nblocks), dim3(kBlock), 0, st, m, sc, xBar, z, u, x, partials, k.xcdMap);
       });
     });
   });
@@ -606,18 +602,15 @@ void launch_energy(const DeviceMesh<D>& m, const double* x, double* partials, in
   });
 }
 template <int D>
-void launch_euler_apply(const DeviceMesh<D>& m, const double* gs, double* x, double dt_over_tau,
+void launch_euler_apply(const DeviceMesh<D>& m, const EngineKnobs& k, const double* gs, double* x, double dt_over_tau,
                         hipStream_t st) {
   if (m.nP == 0) return;
-  hipLaunchKernelGGL(k_euler_apply<D>, dim3(nblk_xcd(m.nP)), dim3(kBlock), 0, st, m, gs, x, dt_over_tau, xcd_map());
+  hipLaunchKernelGGL(k_euler_apply<D>, dim3(nblk_xcd(m.nP, k.xcdMap)), dim3(kBlock), 0, st, m, gs, x, dt_over_tau,
+                     k.xcdMap);
 }
 // one workgroup per set reads its partials at ~0.1 TB/s (C3: 10 sets of 31 k prox partials took 45 us
 // per step); the split form spreads each set over kRedSplit workgroups
-// MMX_RED_SPLIT_MIN overrides kRedSplitMin (tests force the split form on small meshes)
-static bool split_ok(const RedWork& w, int nblocks) {
-  const char* e = getenv("MMX_RED_SPLIT_MIN");
-  return w.scratch && nblocks >= (e ? atoi(e) : kRedSplitMin);
-}
+static bool split_ok(const RedWork& w, int nblocks) { return w.scratch && nblocks >= w.splitMin; }
 static void reduce_split(const double* partA, size_t stride, int nbA, int nA, double* outA, size_t outStride,
                          const double* partB, int nbB, double* outB, const RedWork& w, hipStream_t st) {
   const int sets = nA + (nbB >= 0 ? 1 : 0);
@@ -659,12 +652,13 @@ void launch_pack_export(int mode, int nExp, const int* expOff, const double* z, 
                                       double*, hipStream_t, const PackZX&);                                           \
   template void launch_gather_z<D>(const DeviceMesh<D>&, const double*, double*, hipStream_t);                        \
   template void launch_grad_simplex<D>(const DeviceMesh<D>&, const double*, double*, bool, double*, int*, hipStream_t); \
-  template void launch_predict<D>(const DeviceMesh<D>&, int, const double*, double*, double*, double*, double,        \
-                                  hipStream_t);                                                                       \
-  template void launch_xupdate<D>(const DeviceMesh<D>&, const StepScalars&, const double*, const double*,             \
-                                  const double*, double*, double*, int*, bool, hipStream_t, bool);                    \
+  template void launch_predict<D>(const DeviceMesh<D>&, const EngineKnobs&, int, const double*, double*, double*,     \
+                                  double*, double, hipStream_t);                                                      \
+  template void launch_xupdate<D>(const DeviceMesh<D>&, const EngineKnobs&, const StepScalars&, const double*,        \
+                                  const double*, const double*, double*, double*, int*, bool, hipStream_t, bool);     \
   template void launch_energy<D>(const DeviceMesh<D>&, const double*, double*, int*, hipStream_t);                    \
-  template void launch_euler_apply<D>(const DeviceMesh<D>&, const double*, double*, double, hipStream_t);
+  template void launch_euler_apply<D>(const DeviceMesh<D>&, const EngineKnobs&, const double*, double*, double,       \
+                                      hipStream_t);
 MMX_INST(2)
 MMX_INST(3)
 }  // namespace mmx

@@ -5,8 +5,6 @@
 
 namespace mmx {
 constexpr int kLdsStride = kBlock + 1;  // padded SoA stride of the LDS Bkinv image
-constexpr int kProxBlock = 64;          // steady-state 2D prox workgroup (round 4, with the isotropic grid and recomputed
-                                        // coordinates: 64 0.322 ms, 128 0.327-0.348, 256 0.366 at C3; round 3: 128 > 256 > 64)
 
 // k x k inverse: unblocked partial-pivot LU + substitution (mirrors the oracle's restatement
 // of Eigen PartialPivLU::inverse, src/Mesh.cpp:816).  Dynamic pivoting: first prox only.

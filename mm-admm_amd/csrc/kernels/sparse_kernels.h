@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../host/knobs.h"  // MatrixKnobs: a launcher takes the switches it depends on, none reads the environment
 #include "layout.h"  // MMX_SPMV_*, MMX_CHAIN_VEC / CODE16
 
 namespace mmx {
@@ -14,9 +15,8 @@ namespace mmx {
 constexpr int kSpmvTile = MMX_SPMV_TILE;
 constexpr int kSpmvBlock = MMX_SPMV_BLOCK;
 // Rows per chunk of the level-scheduled factor/sweeps (one wavefront per chunk) and the size of
-// their persistent grid (wavefronts).
+// their persistent grid (wavefronts): MatrixKnobs::sweepGrid, default kSweepGrid (knobs.h).
 constexpr int kSweepRows = 64;
-constexpr int kSweepGrid = 128;  // measured: 2048 waves of pollers slow the chain 3.7x (profiles/r01/lasolver_tune.txt)
 // Grid of the vector kernels (fixed for a given n, so their partial sums are deterministic).
 constexpr int kVecBlock = 256;
 int vec_grid(int n);
@@ -46,7 +46,8 @@ void launch_spmv2(int epi, int nblk, const int4* desc, const int* ia, const int*
 // ILU numeric factor in the factor pattern (iaf/jaf/dg); amap maps A's entries into it.  perm: rows
 // in forward-level order, padded with -1 to whole chunks of kSweepRows.
 // piv[k] for a lower entry k of row i: {dg[id], iaf[id+1]} of its pivot row id = jaf[k].
-void launch_ilu_factor(const int* ia, const int* ja, const double* a, const int* amap, const int* iaf, const int* jaf,
+void launch_ilu_factor(const MatrixKnobs& k,
+                       const int* ia, const int* ja, const double* a, const int* amap, const int* iaf, const int* jaf,
                        const int* dg, const int2* piv, const int* perm, int nchunks, double* af, unsigned* flags,
                        unsigned epoch, unsigned* ticket, unsigned* err, hipStream_t st);
 
@@ -54,7 +55,8 @@ void launch_ilu_factor(const int* ia, const int* ja, const double* a, const int*
 // entry k indexes tgt[], which holds for each upper entry of k's pivot row (after the diagonal)
 // the position in row i it updates, or -1.
 constexpr int kFacW = 127;
-void launch_ilu_factor_lds(const int* ia, const double* a, const int* amap, const int* iaf, const int* jaf, const int* dg,
+void launch_ilu_factor_lds(const MatrixKnobs& k,
+                           const int* ia, const double* a, const int* amap, const int* iaf, const int* jaf, const int* dg,
                            const int2* piv, const int* toff, const signed char* tgt, const int* perm, int nchunks,
                            double* af, unsigned* flags, unsigned epoch, unsigned* ticket, unsigned* err, hipStream_t st);
 
@@ -63,7 +65,8 @@ void launch_ilu_factor_lds(const int* ia, const double* a, const int* amap, cons
 // row.  Bit-identical to the other factors.  gF (2 x nnz(factor) words, or null): rows publish their
 // diagonal and upper part as epoch-tagged granules there instead of drained stores + a flag.
 constexpr int kFacWaveNL = 32;
-void launch_ilu_factor_wave(const int* ia, const double* a, const int* amap, const int* iaf, const int* dg,
+void launch_ilu_factor_wave(const MatrixKnobs& k,
+                            const int* ia, const double* a, const int* amap, const int* iaf, const int* dg,
                             const int2* piv, const int* jaf, const int* toff, const signed char* tgt, const int* perm,
                             int nrows, double* af, unsigned* flags, uint64_t* gF, unsigned epoch, unsigned* ticket,
                             unsigned* err, hipStream_t st);
@@ -79,7 +82,8 @@ void launch_occupy(int blocks, double ms, double* sink, hipStream_t st);
 // Sweep over the rows of perm (forward or backward level order).  Forward: unit L into granules
 // gout, right-hand side per pro (0: src; 1: p = res + beta (p - omega avbar); 2: s = res - alpha
 // avbar, stored to p).  Backward: U from the forward granules gin into out and granules gout.
-void launch_sweep(bool fwd, int pro, const int* iaf, const int* jaf, const int* dg, const double* af, const int* perm,
+void launch_sweep(const MatrixKnobs& k,
+                  bool fwd, int pro, const int* iaf, const int* jaf, const int* dg, const double* af, const int* perm,
                   int nchunks, const double* src, double* p, const double* res, const double* avbar, const CgsScalars* sc,
                   const uint64_t* gin, uint64_t* gout, double* out, unsigned epoch, unsigned* ticket, unsigned* err,
                   hipStream_t st);

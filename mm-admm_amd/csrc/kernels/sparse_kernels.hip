@@ -77,15 +77,6 @@ __device__ __forceinline__ int take_ticket(unsigned* ticket) {
 
 }  // namespace
 
-int sweep_grid() {  // persistent wavefronts of the factor/sweeps (MMX_SWEEP_GRID overrides)
-  static int g = [] {
-    const char* e = getenv("MMX_SWEEP_GRID");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : kSweepGrid;
-  }();
-  return g;
-}
-
 int vec_grid(int n) {
   const int g = (n + kVecBlock - 1) / kVecBlock;
   return g < 1 ? 1 : (g > 1024 ? 1024 : g);
@@ -893,32 +884,29 @@ void launch_spmv2(int epi, int nblk, const int4* desc, const int* ia, const int*
     hipLaunchKernelGGL(k_spmv2<2>, g, bl, 0, st, desc, nblk, ia, ja, a, x, y, e1, partials);
 }
 
-void launch_ilu_factor_lds(const int* ia, const double* a, const int* amap, const int* iaf, const int* jaf, const int* dg,
+void launch_ilu_factor_lds(const MatrixKnobs& k,
+                           const int* ia, const double* a, const int* amap, const int* iaf, const int* jaf, const int* dg,
                            const int2* piv, const int* toff, const signed char* tgt, const int* perm, int nchunks,
                            double* af, unsigned* flags, unsigned epoch, unsigned* ticket, unsigned* err, hipStream_t st) {
   if (nchunks <= 0) return;
-  const int grid = nchunks < sweep_grid() ? nchunks : sweep_grid();
+  const int grid = nchunks < k.sweepGrid ? nchunks : k.sweepGrid;
   hipLaunchKernelGGL((k_ilu_factor_lds<8, 8>), dim3(grid), dim3(kSweepRows), 0, st, ia, a, amap, iaf, jaf, dg, piv, toff,
                      tgt, perm, nchunks, af, flags, epoch, ticket, err);
 }
 
-// tickets of the wave factor: 0 = per workgroup, 4 rows (one per wave); n > 0 = per wave, n
-// consecutive rows (MMX_FAC_CHUNK overrides)
-constexpr int kFacWaveChunk = 0;
+// tickets of the wave factor (MatrixKnobs::facChunk): 0 = per workgroup, 4 rows (one per wave);
+// n > 0 = per wave, n consecutive rows
 // (the grid's size is a throughput choice only: the tickets need no co-residency)
-static int factor_wg() {  // waves per workgroup of the wave factor (MMX_FAC_WG: 4 or 8)
-  static const int v = [] {
-    const char* e = getenv("MMX_FAC_WG");
-    return (e && atoi(e) == 8) ? 8 : 4;
-  }();
-  return v;
-}
-int ilu_factor_wave_grid() {
-  static int g = [] {
+// wg: waves per workgroup of the wave factor (MatrixKnobs::facWg: 4 or 8); found once per process and wg
+static int ilu_factor_wave_grid(int wg) {
+  static int g[2] = {0, 0};
+  int& slot = g[wg == 8 ? 1 : 0];
+  if (slot) return slot;
+  slot = [wg] {
     int dev = 0, cus = 0, nb = 0, nb2 = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (factor_wg() == 8) {
+    if (wg == 8) {
       (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_ilu_factor_wave<kFacWaveNL, true, 8>, 512, 0);
       (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb2, k_ilu_factor_wave<kFacWaveNL, false, 8>, 512, 0);
     } else {
@@ -929,23 +917,21 @@ int ilu_factor_wave_grid() {
     nb = nb < 1 ? 1 : (nb > 8 ? 8 : nb);
     return (cus > 0 ? cus : 1) * nb;
   }();
-  return g;
+  return slot;
 }
 
-void launch_ilu_factor_wave(const int* ia, const double* a, const int* amap, const int* iaf, const int* dg,
+void launch_ilu_factor_wave(const MatrixKnobs& k,
+                            const int* ia, const double* a, const int* amap, const int* iaf, const int* dg,
                             const int2* piv, const int* jaf, const int* toff, const signed char* tgt, const int* perm,
                             int nrows, double* af, unsigned* flags, uint64_t* gF, unsigned epoch, unsigned* ticket,
                             unsigned* err, hipStream_t st) {
   if (nrows <= 0) return;
   // one CU's worth of waves per CU and occupancy slot; rows by ticket (*ticket zeroed by the caller),
-  // MMX_FAC_CHUNK rows per ticket
-  static const int chunk = [] {
-    const char* e = getenv("MMX_FAC_CHUNK");
-    return e ? std::max(0, atoi(e)) : kFacWaveChunk;
-  }();
-  const int wg = chunk > 0 ? 4 : factor_wg();
+  // facChunk rows per ticket
+  const int chunk = k.facChunk;
+  const int wg = chunk > 0 ? 4 : k.facWg;
   const int per = wg * std::max(chunk, 1);  // rows a workgroup takes per round of tickets
-  const int blocks = std::min(ilu_factor_wave_grid(), (nrows + per - 1) / per);
+  const int blocks = std::min(ilu_factor_wave_grid(k.facWg), (nrows + per - 1) / per);
 #define MMX_FACW(G, W)                                                                                           \
   hipLaunchKernelGGL((k_ilu_factor_wave<kFacWaveNL, G, W>), dim3(blocks), dim3(64 * W), 0, st, ia, a, amap, iaf, dg, \
                      piv, jaf, toff, tgt, perm, nrows, chunk, ticket, af, flags, gF, epoch, err)
@@ -1032,21 +1018,23 @@ void launch_occupy(int blocks, double ms, double* sink, hipStream_t st) {
   hipLaunchKernelGGL(k_occupy, dim3(blocks), dim3(1024), 64 * 1024, st, ticks, sink);
 }
 
-void launch_ilu_factor(const int* ia, const int* ja, const double* a, const int* amap, const int* iaf, const int* jaf,
+void launch_ilu_factor(const MatrixKnobs& k,
+                       const int* ia, const int* ja, const double* a, const int* amap, const int* iaf, const int* jaf,
                        const int* dg, const int2* piv, const int* perm, int nchunks, double* af, unsigned* flags,
                        unsigned epoch, unsigned* ticket, unsigned* err, hipStream_t st) {
   if (nchunks <= 0) return;
-  const int grid = nchunks < sweep_grid() ? nchunks : sweep_grid();
+  const int grid = nchunks < k.sweepGrid ? nchunks : k.sweepGrid;
   hipLaunchKernelGGL(k_ilu_factor, dim3(grid), dim3(kSweepRows), 0, st, ia, ja, a, amap, iaf, jaf, dg, piv, perm, nchunks,
                      af, flags, epoch, ticket, err);
 }
 
-void launch_sweep(bool fwd, int pro, const int* iaf, const int* jaf, const int* dg, const double* af, const int* perm,
+void launch_sweep(const MatrixKnobs& k,
+                  bool fwd, int pro, const int* iaf, const int* jaf, const int* dg, const double* af, const int* perm,
                   int nchunks, const double* src, double* p, const double* res, const double* avbar, const CgsScalars* sc,
                   const uint64_t* gin, uint64_t* gout, double* out, unsigned epoch, unsigned* ticket, unsigned* err,
                   hipStream_t st) {
   if (nchunks <= 0) return;
-  const dim3 g(nchunks < sweep_grid() ? nchunks : sweep_grid()), b(kSweepRows);
+  const dim3 g(nchunks < k.sweepGrid ? nchunks : k.sweepGrid), b(kSweepRows);
 #define MMX_SWEEP(F, P)                                                                                              \
   hipLaunchKernelGGL((k_sweep<F, P>), g, b, 0, st, iaf, jaf, dg, af, perm, nchunks, src, p, res, avbar, sc, gin, gout, \
                      out, epoch, ticket, err)

@@ -22,7 +22,7 @@ import ctypes
 
 import numpy as np
 
-from mmadmm_amd import MMADMMError, _check, c_double_p, c_int_p, lib as _mlib
+from mmadmm_amd import MMADMMError, _check, _options, c_double_p, c_int_p, lib as _mlib
 
 _cfg = False
 
@@ -99,6 +99,7 @@ def lib():
     L.mmx_matrix_set_timing.argtypes = [vp, i]
     L.mmx_matrix_stats_get.argtypes = [vp, ctypes.POINTER(SparseStats)]
     L.mmx_matrix_stats_reset.argtypes = [vp]
+    L.mmx_matrix_options_get.argtypes = [vp, ctypes.c_char_p, i]
     L.mmx_matrix_destroy.argtypes = [vp]
     L.mmx_stream_copy.argtypes = [i, vp, vp, ll, i, i, ctypes.POINTER(ctypes.c_double)]
     L.mmx_occupy.argtypes = [i, i, ctypes.c_double]
@@ -307,6 +308,10 @@ class MatrixIter:
 
     def reset_stats(self):
         _check(lib().mmx_matrix_stats_reset(self.h))
+
+    def options(self):
+        """The MMX_* run-time switches as resolved when this matrix was created: {name: value}."""
+        return _options(lib().mmx_matrix_options_get, self.h)
 
     def close(self):
         if lib is None:  # interpreter shutdown

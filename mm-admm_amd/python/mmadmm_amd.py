@@ -107,6 +107,7 @@ def lib():
     L.mmadmm_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.mmadmm_stats_get.argtypes = [ctypes.c_void_p, ctypes.POINTER(mmadmm_stats)]
     L.mmadmm_stats_reset.argtypes = [ctypes.c_void_p]
+    L.mmadmm_options_get.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
     L.mmadmm_sync.argtypes = [ctypes.c_void_p]
     L.mmadmm_regrid.argtypes = [ctypes.c_void_p, ctypes.c_double]
     L.mmadmm_set_regrid.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -183,6 +184,15 @@ def _check(rc):
         if rc == 7:
             raise NonFiniteEnergyError(rc, msg)
         raise MMADMMError(rc, msg)
+
+
+def _options(fn, h):
+    """The "MMX_NAME=value" lines of mmadmm_options_get / mmx_matrix_options_get as a dict."""
+    need = fn(h, None, 0)
+    _check(-need if need < 0 else MMADMM_OK)
+    buf = ctypes.create_string_buffer(need)
+    fn(h, buf, need)
+    return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
 
 
 def _dp(a):
@@ -624,6 +634,10 @@ class Engine:
 
     def reset_stats(self):
         _check(lib().mmadmm_stats_reset(self.h))
+
+    def options(self):
+        """The MMX_* run-time switches as resolved when this engine was created: {name: value}."""
+        return _options(lib().mmadmm_options_get, self.h)
 
     def sync(self):
         _check(lib().mmadmm_sync(self.h))

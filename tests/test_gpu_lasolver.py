@@ -245,7 +245,7 @@ def test_spmv_full_size_bitwise(la):
 
 
 def _sweep_run(la, ia, ja, a, b, mode, monkeypatch):
-    monkeypatch.setenv("MMX_SWEEP", mode)  # read by sfac
+    monkeypatch.setenv("MMX_SWEEP", mode)  # read at create
     A = _matrix(la, ia, ja, a, b)
     p = la.ParamIter.mesh()
     A.sfac(p)

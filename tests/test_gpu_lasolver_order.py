@@ -327,7 +327,7 @@ def test_level_modes_are_bit_identical(la, mats, name, env, monkeypatch):
     p = _param(la, 0)
     x0, it0 = _gpu(mats(name, "a"), p)
     st0 = mats(name, "a").stats()
-    monkeypatch.setenv(env, "level")  # read by sfac
+    monkeypatch.setenv(env, "level")  # read at create
     A = _new(la, name, "a", lorder)
     x, it = _gpu(A, p)
     st = A.stats()

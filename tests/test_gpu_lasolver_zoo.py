@@ -114,7 +114,7 @@ def test_zoo_case_bitwise(la, case, level, shift, monkeypatch):
     for env, em in _modes(s):
         with monkeypatch.context() as m:
             for k, v in env.items():
-                m.setenv(k, v)  # read by sfac
+                m.setenv(k, v)  # read at create
             B, p = _matrix(la, s, level)
             stm = _check_factor_sweeps_solve(B, p, s, em, env)
             B.close()

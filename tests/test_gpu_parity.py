@@ -462,6 +462,8 @@ def test_split_reductions_small_mesh(name, monkeypatch):
     monkeypatch.setenv("MMX_RED_SPLIT_MIN", "1")
     _, Gs = make_pair(mesh, mon, dt, tau, rho, comp, 1, 1)
     _, Gs2 = make_pair(mesh, mon, dt, tau, rho, comp, 1, 1)
+    # (an engine's switches are fixed when it is created: G keeps the one-workgroup path)
+    assert G.options()["MMX_RED_SPLIT_MIN"] == "4096" and Gs.options()["MMX_RED_SPLIT_MIN"] == "1"
     for s in range(3):
         for tol in (-1.0, 1e-3):  # the deferred whole-step reduction and the per-iteration one
             ih_o, it_o = O.step(5, tol)[:2]
@@ -473,3 +475,4 @@ def test_split_reductions_small_mesh(name, monkeypatch):
     np.testing.assert_array_equal(Gs.get("x"), O.get("x"))
     assert Gs.stats()["bfgs_iters"] == O.bfgs_iters() == Gs2.stats()["bfgs_iters"]
     assert Gs.stats()["last_primal"] == Gs2.stats()["last_primal"]
+    assert G.options()["MMX_RED_SPLIT_MIN"] == "4096" and Gs.options()["MMX_RED_SPLIT_MIN"] == "1"

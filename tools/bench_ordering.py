@@ -13,7 +13,7 @@ one work vector: 16 nnz + 20 n + 4).
 
     python tools/bench_ordering.py [--systems 2d,c4] [--orders natural,rcm] [--repeats 3]
 
-MMX_SWEEP=level / MMX_FACTOR=level (read by sfac) select the level-scheduled kernels, as everywhere.
+MMX_SWEEP=level / MMX_FACTOR=level (read when the matrix is created) select the level-scheduled kernels, as everywhere.
 With --orders natural only calls older than the ordering interface are made.
 """
 import argparse
