@@ -8,10 +8,13 @@
 // within 2^-95 of a rounding midpoint (arguments a few ulps from 1 do this systematically),
 // an exact comparison decides the rounding: x^(p/q) > m  <=>  x^p > m^q, evaluated with
 // Shewchuk expansion arithmetic.  The result is the correctly rounded power (round to nearest,
-// ties to even); tests/test_crmath.py and tests/test_gpu_parity.py check it against
-// __float128 powq.  This matters: the first prox builds a finite-difference Hessian with
-// h = 2*sqrt(eps) (reference src/Mesh.cpp:780), which amplifies any last-bit difference in
-// the gradient by 1/h ~ 3e7.
+// ties to even).  Checked on arguments built to land near midpoints, exact ties included
+// (tests/crmath_args.py): on the host against __float128 powq by tests/test_crmath.py
+// (tests/cpp/crmath_check.cpp), on the device against the oracle's crpow by
+// tests/test_gpu_crmath.py (both require the fast path to defer, so cr_resolve runs), and on
+// random arguments by tests/test_gpu_parity.py.  This matters: the first prox builds a
+// finite-difference Hessian with h = 2*sqrt(eps) (reference src/Mesh.cpp:780), which amplifies
+// any last-bit difference in the gradient by 1/h ~ 3e7.
 #pragma once
 #include <cmath>
 #include <cstdint>
