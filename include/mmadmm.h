@@ -125,6 +125,39 @@ typedef struct mmadmm_stats {
 int mmadmm_regrid(mmadmm_handle h, double t);
 int mmadmm_set_regrid(mmadmm_handle h, int every_step);
 
+/* The monitor from the caller's arrays (no reference counterpart; DESIGN.md, Monitor from a nodal field):
+ * the same rebuild as mmadmm_regrid -- bounding box, binning, nearest-vertex fill, smoothing, stats.regrids
+ * += 1 -- with the monitor at the engine's current vertices (mmadmm_get "points", in that order) taken
+ *   _values: from nP x D*D row-major tensors M;
+ *   _field:  from a nodal scalar field u (nP doubles): the engine recovers the field's Hessian H on the
+ *            device (volume-weighted gradient recovery applied twice, symmetrised) and uses
+ *            M_v = I + |H_v| / alpha, |H| the matrix absolute value, alpha finite and > 0.
+ * Meant to be used with mmadmm_set_regrid(h, 0), the caller rebuilding before each step (only the
+ * caller knows the new field).  The plain forms take host arrays.  The _device forms take device
+ * arrays: producer_stream / stream is the HIP stream (hipStream_t) that produced the input, and the
+ * engine orders its own stream after it with an event -- the caller does not synchronise; NULL means
+ * the data are ready.  On return the input may be reused: the engine has read or copied it.
+ * mmadmm_field_hessian(_device) returns the recovered symmetric Hessian alone (nP x D*D), e.g. to
+ * choose alpha; mmadmm_get_device is mmadmm_get for "x" and "points" into a device array (so the
+ * caller can evaluate its field where the mesh is); both order a non-NULL stream after the engine's
+ * writes in the same way (NULL: the call returns when they are done).
+ * Single rank only: an element partition is refused (MMADMM_ERR_INVALID), as are a NULL array and an
+ * alpha that is not finite and positive.  Zero-volume simplices are NOT checked (a simplex of zero
+ * volume divides by zero): the engine's positions are those of a mesh mmadmm_step has accepted. */
+int mmadmm_regrid_values(mmadmm_handle h, const double* M);
+int mmadmm_regrid_values_device(mmadmm_handle h, const double* d_M, void* producer_stream);
+int mmadmm_regrid_field(mmadmm_handle h, const double* u, double alpha);
+int mmadmm_regrid_field_device(mmadmm_handle h, const double* d_u, double alpha, void* producer_stream);
+int mmadmm_field_hessian(mmadmm_handle h, const double* u, double* H);
+int mmadmm_field_hessian_device(mmadmm_handle h, const double* d_u, double* d_H, void* stream);
+int mmadmm_get_device(mmadmm_handle h, const char* what, double* d_out, void* consumer_stream);
+/* Host only, no device needed: the same Hessian and monitor on the CPU, in the kernels' arithmetic
+ * (bit-identical to the calls above at the same positions, with F = mmadmm_get_simplices' simplices: F
+ * is used as given, not re-oriented).  H and / or M (nP x D*D) may be NULL; alpha is checked when M is
+ * asked for.  A node no simplex references gets H = 0, M = I. */
+int mmadmm_field_monitor(int dim, int nP, const double* Xp, int nF, const int32_t* F, const double* u,
+                         double alpha, double* H, double* M);
+
 const char* mmadmm_last_error(void);
 int mmadmm_version(void);
 /* provenance (no reference counterpart): "src_hash=<16 hex> git=<describe> arch=gfx950", the hash of

@@ -84,6 +84,19 @@ public:
     // the reference's commented Mesh<D>::setUp hook (src/Mesh.cpp:1006-1014): rebuild the monitor
     // grid from the current mesh at the start of every step (no reference counterpart; off by default)
     void setTimeVarying(bool on) { mmadmm_cxx::check(mmadmm_set_regrid(h_, on ? 1 : 0)); }
+    // the monitor from the caller's arrays at the current vertices (no reference counterpart): nP x D*D
+    // row-major tensors, or a nodal scalar field u (nP values) whose recovered Hessian H gives
+    // M = I + |H| / alpha.  onDevice: the array is in device memory and ready (include/mmadmm.h:
+    // mmadmm_regrid_values / mmadmm_regrid_field and their _device forms)
+    void regridFromValues(const double *M, bool onDevice = false) {
+        mmadmm_cxx::check(onDevice ? mmadmm_regrid_values_device(h_, M, nullptr) : mmadmm_regrid_values(h_, M));
+    }
+    void regridFromField(const double *u, double alpha, bool onDevice = false) {
+        mmadmm_cxx::check(onDevice ? mmadmm_regrid_field_device(h_, u, alpha, nullptr)
+                                   : mmadmm_regrid_field(h_, u, alpha));
+    }
+    // the engine behind this integrator, for the C-ABI calls the reference's class has no name for
+    mmadmm_handle handle() const { return h_; }
 
     double getEnergy() {
         double E = 0;

@@ -15,6 +15,7 @@
 
 #include "../../../include/mmx_sparse.h"
 #include "../kernels/admm_kernels.h"
+#include "../kernels/field_kernels.h"
 #include "../kernels/regrid_kernels.h"
 #include "comm.h"
 #include "common.h"
@@ -56,12 +57,20 @@ struct EngineBase {
   virtual void sync() = 0;
   virtual void regrid(double t) = 0;
   virtual void setRegrid(bool on) = 0;
+  // the monitor at the vertices from the caller's arrays (mmadmm_regrid_values / _field / mmadmm_field_hessian /
+  // mmadmm_get_device): src = kMonValues (nP x D*D tensors) or kMonField (nP values of a scalar field)
+  virtual void regridFrom(int src, const double* p, bool onDevice, double alpha, void* stream) = 0;
+  virtual void fieldHessian(const double* u, double* H, bool onDevice, void* stream) = 0;
+  virtual void getDevice(const std::string& what, double* dOut, void* stream) = 0;
   virtual void debugBlockGrad(int s, const double* z, const double* dx, int flags, double* out) = 0;
   virtual std::string options() const = 0;
 };
 
 // Mesh::reOrientElements (src/Mesh.cpp:243-260): swap F(i,1), F(i,2) when det(E) < 0, E the
 // edge vectors from vertex 0 as columns, Eigen's 2x2 / 3x3 determinant
+// the source of the monitor at the vertices of a grid rebuild (regridAll)
+enum MonSource { kMonBuiltin7 = 0, kMonCallback = 1, kMonValues = 2, kMonField = 3 };
+
 void reorient_simplices(int D, const double* Vp, int nF, int32_t* F) {
   for (int s = 0; s < nF; ++s) {
     double E[3][3] = {{0}};
@@ -317,6 +326,8 @@ class Engine final : public EngineBase {
     if (jac_) (void)mmx_matrix_destroy(jac_);
     for (auto& e : evPool_) (void)hipEventDestroy(e);
     if (evSync_) (void)hipEventDestroy(evSync_);
+    if (evIn_) (void)hipEventDestroy(evIn_);
+    if (evOut_) (void)hipEventDestroy(evOut_);
     if (resH_) (void)hipHostFree(resH_);
     if (evProx_) (void)hipEventDestroy(evProx_);
     if (evEx_) (void)hipEventDestroy(evEx_);
@@ -1024,6 +1035,85 @@ class Engine final : public EngineBase {
     regridAll(t);
   }
 
+  // the caller's stream -> the engine's: an event recorded on the producer, waited on by st_ (no host
+  // sync); NULL = the data are ready.  The other way for results the caller's stream consumes; NULL
+  // there waits on the host.
+  void afterProducer(void* stream) {
+    if (!stream) return;
+    if (!evIn_) MMX_HIP(hipEventCreateWithFlags(&evIn_, hipEventDisableTiming));
+    MMX_HIP(hipEventRecord(evIn_, (hipStream_t)stream));
+    MMX_HIP(hipStreamWaitEvent(st_, evIn_, 0));
+  }
+  void beforeConsumer(void* stream) {
+    if (!stream) {
+      streamWait();
+      return;
+    }
+    if (!evOut_) MMX_HIP(hipEventCreateWithFlags(&evOut_, hipEventDisableTiming));
+    MMX_HIP(hipEventRecord(evOut_, st_));
+    MMX_HIP(hipStreamWaitEvent((hipStream_t)stream, evOut_, 0));
+  }
+  void singleRankOnly(const char* what) const {
+    if (nranks_ > 1) throw Error(MMADMM_ERR_INVALID, std::string(what) + ": single rank only (no element partition)");
+  }
+  void fieldScratch() {
+    if (fldE_.p) return;
+    fldE_.alloc(std::max<size_t>(field_ebuf_doubles<D>(nF_), 1));
+    fldG_.alloc((size_t)nP_ * D);
+  }
+
+  // mmadmm_regrid_values / mmadmm_regrid_field (and their _device forms): the rebuild of regridAll
+  // from the caller's monitor tensors, or from the monitor recovered from the caller's nodal field
+  void regridFrom(int src, const double* p, bool onDevice, double alpha, void* stream) override {
+    singleRankOnly(src == kMonField ? "mmadmm_regrid_field" : "mmadmm_regrid_values");
+    const size_t n = (size_t)nP_ * (src == kMonField ? 1 : D * D);
+    if (!onDevice) {  // staged: the host array is copied before the call returns
+      if (fldIn_.n < n) fldIn_.alloc(n);
+      MMX_HIP(hipMemcpyAsync(fldIn_.p, p, n * sizeof(double), hipMemcpyHostToDevice, st_));
+      streamWait();
+      p = fldIn_.p;
+    } else {
+      afterProducer(stream);
+    }
+    srcPtr_ = p;
+    srcAlpha_ = alpha;
+    regridAll(0.0, (MonSource)src);
+    srcPtr_ = nullptr;
+    // the caller's array has been read: by the host wait of updateIso, else here (MMX_ISO=0)
+    if (onDevice && !knobs_.iso) streamWait();
+  }
+
+  // mmadmm_field_hessian: the recovered Hessian alone (nP x D*D)
+  void fieldHessian(const double* u, double* H, bool onDevice, void* stream) override {
+    singleRankOnly("mmadmm_field_hessian");
+    fieldScratch();
+    if (!onDevice) {
+      if (fldIn_.n < (size_t)nP_) fldIn_.alloc(nP_);
+      if (fldOut_.n < (size_t)nP_ * D * D) fldOut_.alloc((size_t)nP_ * D * D);
+      MMX_HIP(hipMemcpyAsync(fldIn_.p, u, (size_t)nP_ * sizeof(double), hipMemcpyHostToDevice, st_));
+      launch_field_hessian<D>(Vp_.p, fldIn_.p, F_.p, nF_, incPtr_.p, incOff_.p, nodeOrder_.p, nP_, fldE_.p, fldG_.p, 1.0,
+                              fldOut_.p, nullptr, st_);
+      MMX_HIP(hipGetLastError());
+      MMX_HIP(hipMemcpyAsync(H, fldOut_.p, (size_t)nP_ * D * D * sizeof(double), hipMemcpyDeviceToHost, st_));
+      streamWait();
+      return;
+    }
+    afterProducer(stream);
+    launch_field_hessian<D>(Vp_.p, u, F_.p, nF_, incPtr_.p, incOff_.p, nodeOrder_.p, nP_, fldE_.p, fldG_.p, 1.0, H,
+                            nullptr, st_);
+    MMX_HIP(hipGetLastError());
+    beforeConsumer(stream);
+  }
+
+  // mmadmm_get_device: "x" or "points" into the caller's device array
+  void getDevice(const std::string& what, double* dOut, void* stream) override {
+    singleRankOnly("mmadmm_get_device");
+    const DevBuf<double>* b = what == "x" ? &x_ : what == "points" ? &Vp_ : nullptr;
+    if (!b) throw Error(MMADMM_ERR_INVALID, "mmadmm_get_device: unknown field '" + what + "' (x, points)");
+    MMX_HIP(hipMemcpyAsync(dOut, b->p, (size_t)nP_ * D * sizeof(double), hipMemcpyDeviceToDevice, st_));
+    beforeConsumer(stream);
+  }
+
   // the partitioned rebuild from the candidates near this rank's box; false: fall back (collective)
   bool regridNear(double t) {
     constexpr int DD = D * D;
@@ -1321,7 +1411,7 @@ class Engine final : public EngineBase {
 
   // every vertex: on one rank its own; on a partition each rank's owned vertices all-gathered to
   // every rank (the fallback of regridNear, and MMX_REGRID_GATHER=all)
-  void regridAll(double t) {
+  void regridAll(double t, MonSource src = kMonCallback) {
     constexpr int DD = D * D;
     const int nG = (nranks_ > 1) ? plan_.nP : nP_;  // vertices the grid is built from
     const int nb = std::max(1, std::min(256, (nG + 255) / 256));
@@ -1403,7 +1493,16 @@ class Engine final : public EngineBase {
     launch_bin<D>(X, nG, cg, rgCellOf_.p, rgCounts_.p, rgStarts_.p, rgFill_.p, rgNodes_.p, rgScan_.p, rgScanBytes_,
                   st_);
     // the monitor at the vertices (MonitorFunction::evaluateAtVertices, src/MonitorFunction.cpp:16-32)
-    if (builtin_monitor_kind(monFn_, monUser_) == 7) {
+    // its source: the engine's monitor (built-in 7 on the device, else the host callback), or the
+    // caller's arrays (regridFrom): tensors copied, or recovered from a nodal field (field_kernels.hip)
+    if (src == kMonCallback && builtin_monitor_kind(monFn_, monUser_) == 7) src = kMonBuiltin7;
+    if (src == kMonValues) {
+      MMX_HIP(hipMemcpyAsync(rgMon_.p, srcPtr_, (size_t)nG * DD * sizeof(double), hipMemcpyDeviceToDevice, st_));
+    } else if (src == kMonField) {
+      fieldScratch();
+      launch_field_hessian<D>(X, srcPtr_, F_.p, nF_, incPtr_.p, incOff_.p, nodeOrder_.p, nP_, fldE_.p, fldG_.p,
+                              srcAlpha_, nullptr, rgMon_.p, st_);
+    } else if (src == kMonBuiltin7) {
       double c[3];
       moving_bump_centre(t, c);
       launch_monitor_tv<D>(X, nG, c, rgMon_.p, st_);
@@ -1620,6 +1719,12 @@ class Engine final : public EngineBase {
   void* monUser_ = nullptr;
   bool regridEachStep_ = false, gridOnDevice_ = false;
   DevBuf<double> rgPart_, rgMon_, rgTmp_, rgTmp2_, rgXg_, rgSend_, rgRecv_;
+  // the monitor from the caller's arrays (regridFrom): the element buffer and nodal gradient of the
+  // recovery, staged host input / output, the source of the rebuild in flight, the caller-stream events
+  DevBuf<double> fldE_, fldG_, fldIn_, fldOut_;
+  const double* srcPtr_ = nullptr;
+  double srcAlpha_ = 1.0;
+  hipEvent_t evIn_ = nullptr, evOut_ = nullptr;
   double extMax_[3] = {0.0, 0.0, 0.0};  // widest local simplex per axis (partitioned regrid box), per rebuild
   DevBuf<int> ownLocal_, ownAllGid_;  // partitioned regrid: my owned vertices (local ids), all ranks' (global ids)
   std::vector<int> ownAllGidH_, ownGidH_;
@@ -1883,6 +1988,54 @@ int mmadmm_regrid(mmadmm_handle h, double t) {
 }
 int mmadmm_set_regrid(mmadmm_handle h, int every_step) {
   return guarded([&] { eng(h).setRegrid(every_step != 0); });
+}
+int mmadmm_regrid_values(mmadmm_handle h, const double* M) {
+  return guarded([&] {
+    if (!M) throw Error(MMADMM_ERR_INVALID, "mmadmm_regrid_values: M is NULL");
+    eng(h).regridFrom(mmx::kMonValues, M, false, 1.0, nullptr);
+  });
+}
+int mmadmm_regrid_values_device(mmadmm_handle h, const double* d_M, void* producer_stream) {
+  return guarded([&] {
+    if (!d_M) throw Error(MMADMM_ERR_INVALID, "mmadmm_regrid_values_device: d_M is NULL");
+    eng(h).regridFrom(mmx::kMonValues, d_M, true, 1.0, producer_stream);
+  });
+}
+static void check_alpha(const char* who, double alpha) {
+  if (!(std::isfinite(alpha) && alpha > 0))
+    throw Error(MMADMM_ERR_INVALID, std::string(who) + ": alpha must be finite and > 0");
+}
+int mmadmm_regrid_field(mmadmm_handle h, const double* u, double alpha) {
+  return guarded([&] {
+    if (!u) throw Error(MMADMM_ERR_INVALID, "mmadmm_regrid_field: u is NULL");
+    check_alpha("mmadmm_regrid_field", alpha);
+    eng(h).regridFrom(mmx::kMonField, u, false, alpha, nullptr);
+  });
+}
+int mmadmm_regrid_field_device(mmadmm_handle h, const double* d_u, double alpha, void* producer_stream) {
+  return guarded([&] {
+    if (!d_u) throw Error(MMADMM_ERR_INVALID, "mmadmm_regrid_field_device: d_u is NULL");
+    check_alpha("mmadmm_regrid_field_device", alpha);
+    eng(h).regridFrom(mmx::kMonField, d_u, true, alpha, producer_stream);
+  });
+}
+int mmadmm_field_hessian(mmadmm_handle h, const double* u, double* H) {
+  return guarded([&] {
+    if (!u || !H) throw Error(MMADMM_ERR_INVALID, "mmadmm_field_hessian: NULL array");
+    eng(h).fieldHessian(u, H, false, nullptr);
+  });
+}
+int mmadmm_field_hessian_device(mmadmm_handle h, const double* d_u, double* d_H, void* stream) {
+  return guarded([&] {
+    if (!d_u || !d_H) throw Error(MMADMM_ERR_INVALID, "mmadmm_field_hessian_device: NULL array");
+    eng(h).fieldHessian(d_u, d_H, true, stream);
+  });
+}
+int mmadmm_get_device(mmadmm_handle h, const char* what, double* d_out, void* consumer_stream) {
+  return guarded([&] {
+    if (!what || !d_out) throw Error(MMADMM_ERR_INVALID, "mmadmm_get_device: NULL argument");
+    eng(h).getDevice(what, d_out, consumer_stream);
+  });
 }
 int mmadmm_sync(mmadmm_handle h) {
   return guarded([&] { eng(h).sync(); });

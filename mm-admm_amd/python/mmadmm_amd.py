@@ -111,6 +111,15 @@ def lib():
     L.mmadmm_sync.argtypes = [ctypes.c_void_p]
     L.mmadmm_regrid.argtypes = [ctypes.c_void_p, ctypes.c_double]
     L.mmadmm_set_regrid.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.mmadmm_regrid_values.argtypes = [ctypes.c_void_p, c_double_p]
+    L.mmadmm_regrid_values_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.mmadmm_regrid_field.argtypes = [ctypes.c_void_p, c_double_p, ctypes.c_double]
+    L.mmadmm_regrid_field_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p]
+    L.mmadmm_field_hessian.argtypes = [ctypes.c_void_p, c_double_p, c_double_p]
+    L.mmadmm_field_hessian_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.mmadmm_get_device.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.mmadmm_field_monitor.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_int_p, c_double_p,
+                                       ctypes.c_double, c_double_p, c_double_p]
     L.mmadmm_destroy.argtypes = [ctypes.c_void_p]
     L.mmadmm_mesh_rect.argtypes = [ctypes.c_int] * 4 + [ctypes.c_double] * 6 + [ctypes.c_int,
                                                                                  ctypes.POINTER(ctypes.c_void_p)]
@@ -201,6 +210,31 @@ def _dp(a):
 
 def _ip(a):
     return a.ctypes.data_as(c_int_p)
+
+
+def field_monitor(Xp, F, u, alpha=None, hessian=True, monitor=True):
+    """mmadmm_field_monitor (host only, no device): the Hessian H of the nodal scalar field u recovered
+    on the mesh (Xp, F) and the monitor M = I + |H| / alpha, each nP x D x D -> (H, M); the one not
+    asked for (hessian / monitor False, or alpha None) is None.  F is used as given: pass
+    Engine.simplices() to reproduce an engine's result bit for bit."""
+    Xp = np.ascontiguousarray(Xp, dtype=np.float64)
+    F = np.ascontiguousarray(F, dtype=np.int32)
+    u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+    nP, D = Xp.shape
+    if u.shape[0] != nP or F.ndim != 2 or F.shape[1] != D + 1:
+        raise ValueError("field_monitor: Xp nP x D, F nF x (D + 1), u nP values")
+    H = np.zeros((nP, D, D)) if hessian else None
+    M = np.zeros((nP, D, D)) if (monitor and alpha is not None) else None
+    _check(lib().mmadmm_field_monitor(D, nP, _dp(Xp), F.shape[0], _ip(F), _dp(u),
+                                      float(alpha) if alpha is not None else 1.0,
+                                      _dp(H) if H is not None else None, _dp(M) if M is not None else None))
+    return H, M
+
+
+def _is_tensor(a):
+    """a torch tensor, without importing torch for callers that never pass one"""
+    t = type(a)
+    return t.__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr")
 
 
 # ---------------------------------------------------------------- meshes (src/MeshUtils.h)
@@ -556,6 +590,8 @@ class Engine:
         _check(L.mmadmm_sizes(h, ctypes.byref(nP), ctypes.byref(nF), ctypes.byref(gr)))
         self.nP, self.nF, self.gridRows = nP.value, nF.value, gr.value
         self.K = self.dim * (self.dim + 1)
+        self.device = mesh.device  # HIP ordinal, -1: the current device
+        self._side = None  # torch side stream of the tensor calls made on torch's default stream
 
     def local_nodes(self):
         """Global ids of this engine's nodes (all nodes for a single-GPU engine)."""
@@ -650,6 +686,109 @@ class Engine:
     def set_regrid(self, every_step=True):
         """Time-varying monitor: rebuild the grid at the start of every step, t = steps * dt."""
         _check(lib().mmadmm_set_regrid(self.h, 1 if every_step else 0))
+
+    # -- the monitor from the caller's arrays (include/mmadmm.h: mmadmm_regrid_values / _field ...): a
+    # numpy array goes through the host call, a torch tensor on the engine's GPU through the _device
+    # call on torch's current stream, with no synchronisation here
+    def _device_arg(self, a, n, who):
+        """(pointer, stream handle, stream to rejoin or None) of a float64 contiguous CUDA tensor of n
+        values on the engine's device; anything else raises ValueError."""
+        import torch
+
+        if a.dtype != torch.float64 or not a.is_cuda or not a.is_contiguous() or a.numel() != n:
+            raise ValueError(f"{who}: a torch tensor must be float64, contiguous, on the GPU, with {n} values "
+                             f"(got {a.dtype}, {a.device}, {a.numel()} values)")
+        if self.device is not None and self.device >= 0 and a.device.index != self.device:
+            raise ValueError(f"{who}: tensor on {a.device}, the engine on device {self.device}")
+        cur = torch.cuda.current_stream(a.device)
+        if cur.cuda_stream != 0:
+            return a.data_ptr(), cur.cuda_stream, None
+        # torch's default stream is the null stream, which the ABI reads as "the data are ready": go
+        # through a side stream ordered after it instead (still no host synchronisation)
+        if self._side is None:
+            self._side = torch.cuda.Stream(a.device)
+        self._side.wait_stream(cur)
+        a.record_stream(self._side)
+        return a.data_ptr(), self._side.cuda_stream, (cur, self._side)
+
+    @staticmethod
+    def _rejoin(j):
+        if j is not None:
+            j[0].wait_stream(j[1])
+
+    def regrid_values(self, M):
+        """Rebuild the monitor grid from the monitor tensors M (nP x D x D) at the current vertices
+        (get("points") order): a numpy array, or a float64 CUDA tensor (read on the device, ordered
+        after torch's current stream)."""
+        n = self.nP * self.dim * self.dim
+        if _is_tensor(M):
+            p, st, j = self._device_arg(M, n, "regrid_values")
+            _check(lib().mmadmm_regrid_values_device(self.h, p, st))
+            self._rejoin(j)
+            return
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        if M.size != n:
+            raise ValueError(f"regrid_values: M must hold {n} values")
+        _check(lib().mmadmm_regrid_values(self.h, _dp(M)))
+
+    def field_hessian(self, u):
+        """The Hessian of the nodal scalar field u (nP values) recovered on the current mesh, nP x D x D:
+        a tensor for a tensor, an array for an array."""
+        if _is_tensor(u):
+            import torch
+
+            p, st, j = self._device_arg(u, self.nP, "field_hessian")
+            H = torch.empty((self.nP, self.dim, self.dim), dtype=torch.float64, device=u.device)
+            if j is not None:
+                H.record_stream(j[1])
+            _check(lib().mmadmm_field_hessian_device(self.h, p, H.data_ptr(), st))
+            self._rejoin(j)
+            return H
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+        if u.size != self.nP:
+            raise ValueError(f"field_hessian: u must hold {self.nP} values")
+        H = np.zeros((self.nP, self.dim, self.dim))
+        _check(lib().mmadmm_field_hessian(self.h, _dp(u), _dp(H)))
+        return H
+
+    def regrid_field(self, u, alpha=None):
+        """Rebuild the monitor grid from the nodal scalar field u: M = I + |H| / alpha, H the recovered
+        Hessian.  alpha None: the mean Frobenius norm of field_hessian(u) (1.0 when that is 0).
+        Returns the alpha used."""
+        if alpha is None:
+            H = self.field_hessian(u)
+            if _is_tensor(H):
+                alpha = float((H * H).sum(dim=(1, 2)).sqrt().mean())
+            else:
+                alpha = float(np.sqrt((H * H).sum(axis=(1, 2))).mean())
+            if alpha == 0.0:
+                alpha = 1.0
+        alpha = float(alpha)
+        if _is_tensor(u):
+            p, st, j = self._device_arg(u, self.nP, "regrid_field")
+            _check(lib().mmadmm_regrid_field_device(self.h, p, alpha, st))
+            self._rejoin(j)
+            return alpha
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+        if u.size != self.nP:
+            raise ValueError(f"regrid_field: u must hold {self.nP} values")
+        _check(lib().mmadmm_regrid_field(self.h, _dp(u), alpha))
+        return alpha
+
+    def get_tensor(self, what):
+        """get("points" | "x") as a float64 CUDA tensor (nP x D), copied on the device and ordered
+        before torch's current stream."""
+        import torch
+
+        if what not in ("points", "x"):
+            raise ValueError("get_tensor: 'points' or 'x'")
+        dev = torch.device("cuda", self.device if self.device is not None and self.device >= 0
+                           else torch.cuda.current_device())
+        out = torch.empty((self.nP, self.dim), dtype=torch.float64, device=dev)
+        p, st, j = self._device_arg(out, self.nP * self.dim, "get_tensor")
+        _check(lib().mmadmm_get_device(self.h, what.encode(), p, st))
+        self._rejoin(j)
+        return out
 
     def block_grad(self, sid, z, dxpu=None, computeGrad=True, regularize=False):
         """Device Mesh::computeBlockGrad of one simplex -> (energy, grad, Igt)."""
