@@ -158,6 +158,35 @@ int mmadmm_get_device(mmadmm_handle h, const char* what, double* d_out, void* co
 int mmadmm_field_monitor(int dim, int nP, const double* Xp, int nF, const int32_t* F, const double* u,
                          double alpha, double* H, double* M);
 
+/* ---- nodal fields onto the moved mesh (no reference counterpart)
+ * After mmadmm_step the nodes have moved and u[v] still holds the caller's field at the old position
+ * of node v.  mmadmm_transfer evaluates the piecewise-linear field (old positions Xold, nP x D;
+ * values uold, nP x C row-major, C >= 1) at the new positions Xnew (NULL: the engine's current
+ * "points") into unew (nP x C), on the device: a node whose position did not change bit for bit, or
+ * that no simplex references, is copied; else the first of its incident simplices (ascending id)
+ * that contains the new position to -1e-12 in every barycentric coordinate is used; else a walk over
+ * face neighbours from the best of them, at most 64 moves.  A node the walk does not locate (it left
+ * the mesh; the walk does not go round a re-entrant boundary) is extrapolated linearly from the
+ * best simplex seen.  where (nP, may be NULL): -1 copied, s >= 0 the simplex used, -2 - s outside.
+ * counts (4 ints on the host, may be NULL): {copied, found in the patch, walked, outside}; asking
+ * for it costs one small read-back.  The _device form reads and writes device arrays (2D: positions
+ * 16-byte aligned) ordered after `stream`'s work and hands the results back to it with no host
+ * synchronisation (unless counts is asked for); stream NULL: the data are ready, and the call returns
+ * when the results are.  Bitwise reproducible.  Refused (MMADMM_ERR_INVALID): C < 1, a NULL required
+ * array, unew == uold, an element partition (single rank only).  Zero- or negative-volume old
+ * simplices are NOT checked. */
+int mmadmm_transfer(mmadmm_handle h, const double* Xold, const double* Xnew, int C, const double* uold, double* unew,
+                    int32_t* where, int* counts);
+int mmadmm_transfer_device(mmadmm_handle h, const double* d_Xold, const double* d_Xnew, int C, const double* d_uold,
+                           double* d_unew, int32_t* d_where, int* counts, void* stream);
+/* Host only, no device needed: the same transfer on the CPU in the kernels' arithmetic (bit-identical
+ * to the calls above with F = mmadmm_get_simplices' simplices: F is used as given, not re-oriented). */
+int mmadmm_transfer_field(int dim, int nP, const double* Xold, int nF, const int32_t* F, const double* Xnew, int C,
+                          const double* uold, double* unew, int32_t* where, int* counts);
+/* The face-neighbour table the transfer walks (host only): nbr[s (dim + 1) + j] = the simplex sharing
+ * the face of s opposite its local vertex j, or -1. */
+int mmadmm_face_neighbours(int dim, int nP, int nF, const int32_t* F, int32_t* nbr);
+
 const char* mmadmm_last_error(void);
 int mmadmm_version(void);
 /* provenance (no reference counterpart): "src_hash=<16 hex> git=<describe> arch=gfx950", the hash of

@@ -95,6 +95,14 @@ public:
         mmadmm_cxx::check(onDevice ? mmadmm_regrid_field_device(h_, u, alpha, nullptr)
                                    : mmadmm_regrid_field(h_, u, alpha));
     }
+    // the caller's nodal field (C components per node, nP x C row-major) carried from the node
+    // positions Xold (nP x D row-major, e.g. those before step()) to the current ones, piecewise
+    // linearly on the old mesh (no reference counterpart; include/mmadmm.h: mmadmm_transfer and
+    // mmadmm_transfer_device).  onDevice: all three arrays are in device memory and ready
+    void transferField(const double *Xold, int C, const double *uold, double *unew, bool onDevice = false) {
+        mmadmm_cxx::check(onDevice ? mmadmm_transfer_device(h_, Xold, nullptr, C, uold, unew, nullptr, nullptr, nullptr)
+                                   : mmadmm_transfer(h_, Xold, nullptr, C, uold, unew, nullptr, nullptr));
+    }
     // the engine behind this integrator, for the C-ABI calls the reference's class has no name for
     mmadmm_handle handle() const { return h_; }
 

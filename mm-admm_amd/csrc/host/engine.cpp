@@ -17,9 +17,11 @@
 #include "../kernels/admm_kernels.h"
 #include "../kernels/field_kernels.h"
 #include "../kernels/regrid_kernels.h"
+#include "../kernels/transfer_kernels.h"
 #include "comm.h"
 #include "common.h"
 #include "partition.h"
+#include "transfer.h"
 #include "xup_records.h"
 
 #define MMX_SP(expr)                                                                     \
@@ -62,6 +64,9 @@ struct EngineBase {
   virtual void regridFrom(int src, const double* p, bool onDevice, double alpha, void* stream) = 0;
   virtual void fieldHessian(const double* u, double* H, bool onDevice, void* stream) = 0;
   virtual void getDevice(const std::string& what, double* dOut, void* stream) = 0;
+  // mmadmm_transfer(_device): nodal fields from the old node positions to the new ones (Xnew null: Vp)
+  virtual void transfer(const double* Xold, const double* Xnew, int C, const double* uold, double* unew, int32_t* where,
+                        int* counts, bool onDevice, void* stream) = 0;
   virtual void debugBlockGrad(int s, const double* z, const double* dx, int flags, double* out) = 0;
   virtual std::string options() const = 0;
 };
@@ -1105,6 +1110,52 @@ class Engine final : public EngineBase {
     beforeConsumer(stream);
   }
 
+  // the face-neighbour table (built from the simplices at the first transfer of an engine, uploaded
+  // once), the marks of a call without `where`, and the slotted counts
+  void transferScratch() {
+    if (trNbr_.p) return;
+    trNbrH_.assign(std::max<size_t>((size_t)nF_ * (D + 1), 1), -1);
+    build_face_neighbours(D, nF_, plan_.Flocal.data(), trNbrH_.data());
+    trNbr_.upload(trNbrH_.data(), trNbrH_.size(), st_);
+    trWhere_.alloc(std::max(nP_, 1));
+    trCnt_.alloc(kTransferCountInts);
+  }
+
+  // mmadmm_transfer / mmadmm_transfer_device (transfer_kernels.hip)
+  void transfer(const double* Xold, const double* Xnew, int C, const double* uold, double* unew, int32_t* where,
+                int* counts, bool onDevice, void* stream) override {
+    const char* who = onDevice ? "mmadmm_transfer_device" : "mmadmm_transfer";
+    singleRankOnly(who);
+    transferScratch();
+    const size_t nx = (size_t)nP_ * D, nu = (size_t)nP_ * C;
+    int cnt[kTransferCountInts];  // the slotted counts (transfer_kernels.h), read back when asked for
+    if (!onDevice) {  // staged through the same kernels; the host arrays are done with when the call returns
+      if (trStage_.n < 2 * nx + 2 * nu) trStage_.alloc(2 * nx + 2 * nu);
+      double *dXo = trStage_.p, *dXn = dXo + nx, *dUo = dXn + nx, *dUn = dUo + nu;
+      MMX_HIP(hipMemcpyAsync(dXo, Xold, nx * sizeof(double), hipMemcpyHostToDevice, st_));
+      if (Xnew) MMX_HIP(hipMemcpyAsync(dXn, Xnew, nx * sizeof(double), hipMemcpyHostToDevice, st_));
+      MMX_HIP(hipMemcpyAsync(dUo, uold, nu * sizeof(double), hipMemcpyHostToDevice, st_));
+      launch_transfer<D>(dXo, Xnew ? dXn : Vp_.p, F_.p, incPtr_.p, incOff_.p, nodeOrder_.p, trNbr_.p, nP_, C, dUo, dUn,
+                         trWhere_.p, trCnt_.p, st_);
+      MMX_HIP(hipGetLastError());
+      MMX_HIP(hipMemcpyAsync(unew, dUn, nu * sizeof(double), hipMemcpyDeviceToHost, st_));
+      if (where) MMX_HIP(hipMemcpyAsync(where, trWhere_.p, (size_t)nP_ * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+      if (counts) MMX_HIP(hipMemcpyAsync(cnt, trCnt_.p, sizeof cnt, hipMemcpyDeviceToHost, st_));
+      streamWait();
+    } else {
+      if (D == 2 && ((((uintptr_t)Xold) | ((uintptr_t)(Xnew ? Xnew : Vp_.p))) & 15))
+        throw Error(MMADMM_ERR_INVALID, std::string(who) + ": 2D position arrays must be 16-byte aligned");
+      afterProducer(stream);
+      launch_transfer<D>(Xold, Xnew ? Xnew : Vp_.p, F_.p, incPtr_.p, incOff_.p, nodeOrder_.p, trNbr_.p, nP_, C, uold, unew,
+                         where ? where : trWhere_.p, trCnt_.p, st_);
+      MMX_HIP(hipGetLastError());
+      if (counts) MMX_HIP(hipMemcpyAsync(cnt, trCnt_.p, sizeof cnt, hipMemcpyDeviceToHost, st_));
+      beforeConsumer(stream);
+      if (counts && stream) streamWait();  // the read-back; without counts the host does not wait
+    }
+    if (counts) transfer_sum_counts(cnt, counts);
+  }
+
   // mmadmm_get_device: "x" or "points" into the caller's device array
   void getDevice(const std::string& what, double* dOut, void* stream) override {
     singleRankOnly("mmadmm_get_device");
@@ -1722,6 +1773,9 @@ class Engine final : public EngineBase {
   // the monitor from the caller's arrays (regridFrom): the element buffer and nodal gradient of the
   // recovery, staged host input / output, the source of the rebuild in flight, the caller-stream events
   DevBuf<double> fldE_, fldG_, fldIn_, fldOut_;
+  std::vector<int32_t> trNbrH_;  // the transfer's face-neighbour table (host copy) and device scratch
+  DevBuf<int32_t> trNbr_, trWhere_, trCnt_;
+  DevBuf<double> trStage_;
   const double* srcPtr_ = nullptr;
   double srcAlpha_ = 1.0;
   hipEvent_t evIn_ = nullptr, evOut_ = nullptr;
@@ -2029,6 +2083,25 @@ int mmadmm_field_hessian_device(mmadmm_handle h, const double* d_u, double* d_H,
   return guarded([&] {
     if (!d_u || !d_H) throw Error(MMADMM_ERR_INVALID, "mmadmm_field_hessian_device: NULL array");
     eng(h).fieldHessian(d_u, d_H, true, stream);
+  });
+}
+static void check_transfer(const char* who, const double* Xold, int C, const double* uold, const double* unew) {
+  if (C < 1) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": C must be >= 1");
+  if (!Xold || !uold || !unew) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": NULL array");
+  if (unew == uold) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": unew must not be uold");
+}
+int mmadmm_transfer(mmadmm_handle h, const double* Xold, const double* Xnew, int C, const double* uold, double* unew,
+                    int32_t* where, int* counts) {
+  return guarded([&] {
+    check_transfer("mmadmm_transfer", Xold, C, uold, unew);
+    eng(h).transfer(Xold, Xnew, C, uold, unew, where, counts, false, nullptr);
+  });
+}
+int mmadmm_transfer_device(mmadmm_handle h, const double* d_Xold, const double* d_Xnew, int C, const double* d_uold,
+                           double* d_unew, int32_t* d_where, int* counts, void* stream) {
+  return guarded([&] {
+    check_transfer("mmadmm_transfer_device", d_Xold, C, d_uold, d_unew);
+    eng(h).transfer(d_Xold, d_Xnew, C, d_uold, d_unew, d_where, counts, true, stream);
   });
 }
 int mmadmm_get_device(mmadmm_handle h, const char* what, double* d_out, void* consumer_stream) {

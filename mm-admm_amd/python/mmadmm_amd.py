@@ -120,6 +120,13 @@ def lib():
     L.mmadmm_get_device.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p]
     L.mmadmm_field_monitor.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_int_p, c_double_p,
                                        ctypes.c_double, c_double_p, c_double_p]
+    L.mmadmm_transfer.argtypes = [ctypes.c_void_p, c_double_p, c_double_p, ctypes.c_int, c_double_p, c_double_p,
+                                  c_int_p, c_int_p]
+    L.mmadmm_transfer_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_int_p, ctypes.c_void_p]
+    L.mmadmm_transfer_field.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_int_p, c_double_p,
+                                        ctypes.c_int, c_double_p, c_double_p, c_int_p, c_int_p]
+    L.mmadmm_face_neighbours.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, c_int_p]
     L.mmadmm_destroy.argtypes = [ctypes.c_void_p]
     L.mmadmm_mesh_rect.argtypes = [ctypes.c_int] * 4 + [ctypes.c_double] * 6 + [ctypes.c_int,
                                                                                  ctypes.POINTER(ctypes.c_void_p)]
@@ -229,6 +236,52 @@ def field_monitor(Xp, F, u, alpha=None, hessian=True, monitor=True):
                                       float(alpha) if alpha is not None else 1.0,
                                       _dp(H) if H is not None else None, _dp(M) if M is not None else None))
     return H, M
+
+
+TRANSFER_COUNTS = ("copied", "patch", "walked", "outside")
+
+
+def _field_2d(u, nP, who):
+    """u as a contiguous nP x C float64 array (a 1-D u is one component)"""
+    u = np.ascontiguousarray(u, dtype=np.float64)
+    if u.ndim not in (1, 2) or u.shape[0] != nP or u.size == 0:
+        raise ValueError(f"{who}: u must be nP or nP x C values (C >= 1), nP = {nP}")
+    return u.reshape(nP, -1)
+
+
+def transfer_field(Xold, F, Xnew, u, where=True):
+    """mmadmm_transfer_field (host only, no device): the piecewise-linear field (old positions Xold,
+    nodal values u: nP or nP x C) evaluated at the new node positions Xnew -> (u_new, info); info holds
+    the counts "copied", "patch", "walked", "outside" and, unless where is False, "where" (-1 copied,
+    s >= 0 the simplex used, -2 - s outside).  F is used as given: pass Engine.simplices() to reproduce
+    Engine.transfer bit for bit."""
+    Xold = np.ascontiguousarray(Xold, dtype=np.float64)
+    Xnew = np.ascontiguousarray(Xnew, dtype=np.float64)
+    F = np.ascontiguousarray(F, dtype=np.int32)
+    if Xold.ndim != 2 or Xnew.shape != Xold.shape or F.ndim != 2 or F.shape[1] != Xold.shape[1] + 1:
+        raise ValueError("transfer_field: Xold, Xnew nP x D, F nF x (D + 1)")
+    nP, D = Xold.shape
+    shape = np.shape(u)
+    u2 = _field_2d(u, nP, "transfer_field")
+    out = np.zeros_like(u2)
+    w = np.zeros(nP, dtype=np.int32) if where else None
+    cnt = np.zeros(4, dtype=np.int32)
+    _check(lib().mmadmm_transfer_field(D, nP, _dp(Xold), F.shape[0], _ip(F), _dp(Xnew), u2.shape[1], _dp(u2), _dp(out),
+                                       _ip(w) if where else None, _ip(cnt)))
+    info = {k: int(c) for k, c in zip(TRANSFER_COUNTS, cnt)}
+    if where:
+        info["where"] = w
+    return out.reshape(shape), info
+
+
+def face_neighbours(F, nP=None):
+    """mmadmm_face_neighbours (host only): nbr[s, j] = the simplex sharing the face of s opposite its
+    local vertex j, or -1."""
+    F = np.ascontiguousarray(F, dtype=np.int32)
+    nbr = np.zeros_like(F)
+    _check(lib().mmadmm_face_neighbours(F.shape[1] - 1, int(F.max()) + 1 if nP is None else nP, F.shape[0], _ip(F),
+                                        _ip(nbr)))
+    return nbr
 
 
 def _is_tensor(a):
@@ -774,6 +827,57 @@ class Engine:
             raise ValueError(f"regrid_field: u must hold {self.nP} values")
         _check(lib().mmadmm_regrid_field(self.h, _dp(u), alpha))
         return alpha
+
+    def transfer(self, u, X_old, X_new=None, where=False):
+        """The nodal field u (nP or nP x C values at the old node positions X_old, nP x D) evaluated at the
+        new node positions X_new (None: the engine's current "points"), piecewise linearly on the old
+        mesh (include/mmadmm.h: mmadmm_transfer) -> (u_new, info).  Numpy arrays go through the host
+        call, float64 CUDA tensors through the _device call on torch's current stream; u_new (and
+        info["where"], on request) is of the kind given.  info holds the counts "copied", "patch",
+        "walked", "outside" (reading them waits for the transfer)."""
+        nx = self.nP * self.dim
+        cnt = np.zeros(4, dtype=np.int32)
+        if _is_tensor(u):
+            import torch
+
+            if u.dim() not in (1, 2) or u.shape[0] != self.nP or u.numel() == 0:
+                raise ValueError(f"transfer: u must be nP or nP x C values (C >= 1), nP = {self.nP}")
+            C = u.numel() // self.nP
+            if not _is_tensor(X_old) or not (X_new is None or _is_tensor(X_new)):
+                raise ValueError("transfer: u, X_old and X_new must all be tensors or all be arrays")
+            pu, st, j = self._device_arg(u, self.nP * C, "transfer")
+            po, st, j = self._device_arg(X_old, nx, "transfer")
+            pn = None
+            if X_new is not None:
+                pn, st, j = self._device_arg(X_new, nx, "transfer")
+            out = torch.empty_like(u)
+            w = torch.empty(self.nP, dtype=torch.int32, device=u.device) if where else None
+            if j is not None:
+                out.record_stream(j[1])
+                if where:
+                    w.record_stream(j[1])
+            _check(lib().mmadmm_transfer_device(self.h, po, pn, C, pu, out.data_ptr(), w.data_ptr() if where else None,
+                                                _ip(cnt), st))
+            self._rejoin(j)
+        else:
+            if _is_tensor(X_old) or _is_tensor(X_new):
+                raise ValueError("transfer: u, X_old and X_new must all be tensors or all be arrays")
+            shape = np.shape(u)
+            u2 = _field_2d(u, self.nP, "transfer")
+            X_old = np.ascontiguousarray(X_old, dtype=np.float64)
+            if X_new is not None:
+                X_new = np.ascontiguousarray(X_new, dtype=np.float64)
+            if X_old.size != nx or (X_new is not None and X_new.size != nx):
+                raise ValueError(f"transfer: positions must hold {nx} values")
+            out2 = np.zeros_like(u2)
+            w = np.zeros(self.nP, dtype=np.int32) if where else None
+            _check(lib().mmadmm_transfer(self.h, _dp(X_old), _dp(X_new) if X_new is not None else None, u2.shape[1],
+                                         _dp(u2), _dp(out2), _ip(w) if where else None, _ip(cnt)))
+            out = out2.reshape(shape)
+        info = {k: int(c) for k, c in zip(TRANSFER_COUNTS, cnt)}
+        if where:
+            info["where"] = w
+        return out, info
 
     def get_tensor(self, what):
         """get("points" | "x") as a float64 CUDA tensor (nP x D), copied on the device and ordered
