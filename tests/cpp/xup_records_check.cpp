@@ -3,6 +3,8 @@
 // the slot table, its padding, the records and invdiag by position, and the slot sequence a kernel
 // walks (the table's first ch columns, then inc_off[b + ch ...]) against inc_off[b .. e).
 // Built with -fsanitize=address,undefined by tests/test_xup_records_host.py; prints "ok".
+// Each argument names a mesh file ("D nP nF hubValence" and the nF (D + 1) vertex ids, as text) checked
+// besides the built-in ones: the hub meshes of tests/hub_meshes.py, whose node 0 has 6 .. 168 slots.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -183,11 +185,46 @@ void check_all_orders(const char* name, const Csr& c, int ch) {
   check_records(name, c, &o, ch);
 }
 
+// a mesh file: every chunk size of its dimension, and with every third slot on another rank
+void check_file(const char* path) {
+  std::FILE* fp = std::fopen(path, "r");
+  int D = 0, nP = 0, nF = 0, hub = 0;
+  if (!fp || std::fscanf(fp, "%d %d %d %d", &D, &nP, &nF, &hub) != 4 || (D != 2 && D != 3) || nP < 1 || nF < 1) {
+    CHECK(false, "%s: cannot read the header", path);
+    if (fp) std::fclose(fp);
+    return;
+  }
+  std::vector<int32_t> F((size_t)nF * (D + 1));
+  for (int32_t& v : F) {
+    int id = -1;
+    if (std::fscanf(fp, "%d", &id) != 1 || id < 0 || id >= nP) {
+      CHECK(false, "%s: bad vertex id", path);
+      std::fclose(fp);
+      return;
+    }
+    v = id;
+  }
+  std::fclose(fp);
+  const Csr c = csr_of(D, nP, F);
+  CHECK(c.maxValence() == hub && c.ptr[1] - c.ptr[0] == hub, "%s: valence %d, node 0 has %d, expected %d", path,
+        c.maxValence(), c.ptr[1] - c.ptr[0], hub);
+  Csr n = c;  // slots of another rank, the hub's last one among them
+  int r = 0;
+  for (size_t t = 0; t < n.off.size(); t += 3) n.off[t] = -1 - r++;
+  n.off[n.ptr[1] - 1] = -1 - r;
+  const int chs2[] = {6, 8}, chs3[] = {8, 16, 24};
+  for (int ch : std::vector<int>(D == 2 ? chs2 : chs3, D == 2 ? chs2 + 2 : chs3 + 3)) {
+    check_all_orders(path, c, ch);
+    check_all_orders(path, n, ch);
+  }
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
   int nP = 0;
   std::vector<int32_t> F;
+  for (int i = 1; i < argc; ++i) check_file(argv[i]);
   {  // 3-ring hexagonal disc: every node within one chunk of 6
     hexdisc(3, nP, F);
     const Csr c = csr_of(2, nP, F);

@@ -6,10 +6,10 @@ import pytest
 
 import field_monitor_py as fp
 import mmadmm_amd as mx
-from field_monitor_cases import displaced, field, make_mesh, unreferenced
+from field_monitor_cases import HUB_MESHES, displaced, field, make_mesh, unreferenced
 
 ALPHA = 3.7
-MESHES = ["rect2_8", "rect3_4", "hexdisc6", "shoulder2_8"]
+MESHES = ["rect2_8", "rect3_4", "hexdisc6", "shoulder2_8"] + HUB_MESHES
 _cache = {}
 
 

@@ -7,17 +7,25 @@ import pytest
 import torch  # before the library is loaded: libmmadmm then binds to the HIP runtime torch brought
 
 import mmadmm_amd as mx
-from field_monitor_cases import field, make_mesh, unreferenced
+from field_monitor_cases import HUB_MESHES, field, make_mesh, static_monitor, step_params, unreferenced
 
 pytestmark = pytest.mark.gpu
 
 MESHES = ["rect2_5", "rect2_14", "rect3_4", "hexdisc6", "shoulder2_8"]
+FIELD_MESHES = MESHES + HUB_MESHES  # the recovery's node kernel: one node of 6 .. 168 simplices besides
 ITERS = 5
 
 
-def engine(mesh, mon):
-    M = mx.Mesh(mesh.Xp, mesh.F, mesh.mask, mx.BuiltinMonitor(mesh.dim, mon), rho=1000.0, tau=0.5, device=0)
-    return mx.Engine(M, 0.025)
+# Under the monitor recovered from field() -- far stronger than the built-in ones -- a step of the hub meshes'
+# size inverts a sliver of fan2d(64, 2), fan2d(100, 2) and hub3d(12, 8, 2) within two steps, in both engines
+# alike; at a tenth of it all seven complete the four rounds and move by 6e-4 .. 5e-3
+HUB_FIELD_DT = 0.1
+
+
+def engine(mesh, mon, name="", dt_scale=1.0):
+    dt, rho = step_params(name)  # (a hub mesh: the smaller step its slivers take)
+    M = mx.Mesh(mesh.Xp, mesh.F, mesh.mask, mx.BuiltinMonitor(mesh.dim, mon), rho=rho, tau=0.5, device=0)
+    return mx.Engine(M, dt * dt_scale)
 
 
 def monitor_at(dim, mon, X):
@@ -85,10 +93,10 @@ def test_producer_stream_is_waited_for():
     torch.cuda.synchronize()
 
 
-@pytest.mark.parametrize("name", MESHES)
+@pytest.mark.parametrize("name", FIELD_MESHES)
 def test_device_hessian_equals_host_function(name):
     mesh, _ = make_mesh(name)
-    E = engine(mesh, 1 if mesh.dim == 2 else 3)
+    E = engine(mesh, static_monitor(name, mesh.dim), name)
     for _ in range(2):
         E.step(ITERS, -1.0)
     X = E.get("points").reshape(-1, mesh.dim)
@@ -103,11 +111,12 @@ def test_device_hessian_equals_host_function(name):
         assert lone.size >= 1 and not Hd[lone].any()
 
 
-@pytest.mark.parametrize("name", MESHES)
+@pytest.mark.parametrize("name", FIELD_MESHES)
 def test_field_path_equals_values_path(name):
     mesh, _ = make_mesh(name)
-    mon = 1 if mesh.dim == 2 else 3
-    A, B = engine(mesh, mon), engine(mesh, mon)
+    mon = static_monitor(name, mesh.dim)
+    scale = HUB_FIELD_DT if name in HUB_MESHES else 1.0
+    A, B = engine(mesh, mon, name, scale), engine(mesh, mon, name, scale)
     F = A.simplices()
     alpha = None
     for k in range(4):
@@ -129,6 +138,7 @@ def test_field_path_equals_values_path(name):
             same_state(A, B)
     assert A.stats()["regrids"] == B.stats()["regrids"] == 4
     assert A.stats()["monitor_iso"] == 0
+    assert not np.array_equal(A.get("points").reshape(-1, mesh.dim), mesh.Xp), "the mesh was expected to move"
 
 
 def test_regrid_field_host_array_equals_tensor():

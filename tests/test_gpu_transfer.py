@@ -10,7 +10,7 @@ import pytest
 import torch  # before the library is loaded: libmmadmm then binds to the HIP runtime torch brought
 
 import mmadmm_amd as mx
-from transfer_cases import MESHES, MOVES, fields, make_mesh, moved
+from transfer_cases import ALL_MESHES, CASES, fields, make_mesh, moved, static_monitor, step_params
 
 pytestmark = pytest.mark.gpu
 
@@ -21,14 +21,15 @@ KEYS = mx.TRANSFER_COUNTS
 @functools.lru_cache(maxsize=None)
 def engine_of(name):
     """one engine per mesh, never stepped: its simplices and incidence lists are those of the mesh"""
+    return engine(name)
+
+
+def engine(name):
     mesh, h, F = make_mesh(name)
-    return engine(mesh)
-
-
-def engine(mesh):
-    M = mx.Mesh(mesh.Xp, mesh.F, mesh.mask, mx.BuiltinMonitor(mesh.dim, 1 if mesh.dim == 2 else 3), rho=1000.0, tau=0.5,
+    dt, rho = step_params(name)  # (a hub mesh: the smaller step its slivers take)
+    M = mx.Mesh(mesh.Xp, mesh.F, mesh.mask, mx.BuiltinMonitor(mesh.dim, static_monitor(name, mesh.dim)), rho=rho, tau=0.5,
                 device=0)
-    return mx.Engine(M, 0.025)
+    return mx.Engine(M, dt)
 
 
 def cuda(a):
@@ -50,8 +51,7 @@ def same_result(got, want, what):
 
 
 @pytest.mark.parametrize("C", [1, 3])
-@pytest.mark.parametrize("move", MOVES)
-@pytest.mark.parametrize("name", MESHES)
+@pytest.mark.parametrize("name,move", CASES)
 def test_device_equals_host_function(name, move, C):
     mesh, h, F = make_mesh(name)
     E = engine_of(name)
@@ -70,10 +70,10 @@ def test_device_equals_host_function(name, move, C):
     assert np.array_equal(u2.cpu().numpy(), want[0])
 
 
-@pytest.mark.parametrize("name", MESHES)
+@pytest.mark.parametrize("name", ALL_MESHES)
 def test_engine_motion_end_to_end(name):
     mesh, h, F = make_mesh(name)
-    E = engine(mesh)
+    E = engine(name)
     X0 = E.get_tensor("points")
     for _ in range(2):
         E.step(ITERS, -1.0)
@@ -137,7 +137,7 @@ def test_device_call_without_counts_hands_over_by_stream():
 @pytest.mark.parametrize("name", ["rect2_8", "rect3_4", "hexdisc6"])
 def test_adaptive_loop_on_device_equals_host_transfer(name):
     mesh, h, F = make_mesh(name)
-    A, B = engine(mesh), engine(mesh)
+    A, B = engine(name), engine(name)
     Fe = A.simplices()
     ua = cuda(fields(mesh.Xp, 1)[:, 0].copy())
     ub = ua.cpu().numpy()

@@ -6,7 +6,8 @@ sums keep their order, so everything here is bit for bit:
 * against the oracle (x, z, u) over five steps whose tolerances (-1, 1e-3, -1, -1, -1) run the
   every-iteration residual (step 2) and the fused-predictor first x-update (steps after the third),
   on a hexagonal disc (valence <= 6), 2D square grids (valence 8: the tail past the chunk of 6), a
-  3D grid (valence 24) and a Shoulder mesh (nodes no simplex references);
+  3D grid (valence 24), a Shoulder mesh (nodes no simplex references) and two hub meshes (valence
+  64 and 80);
 * MMX_XUP_REC=0 against the default for the one-node-per-lane form and the sweep (MMX_XUP_SWEEP = 0,
   1, 2), with and without the next node's early request, for both MMX_TSLOT values;
 * a 2-rank loopback partition (interior / interface launches by position, remote slots) against
@@ -21,6 +22,7 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(__file__)), "mm-admm_amd", "python"))
 
+import hub_meshes  # noqa: E402
 import mmadmm_amd as mx  # noqa: E402
 import oracle_py  # noqa: E402
 
@@ -40,6 +42,9 @@ ORACLE_CASES = [
     ("rect2d_6", lambda: mx.MeshData.rect(2, 6), 3, 1000.0, 0.025),
     ("rect3d_4", lambda: mx.MeshData.rect(3, 4), 6, 2000.0, 0.025),
     ("shoulder2d_8", lambda: mx.MeshData.shoulder(2, 8), 1, 50.0, 0.025),
+    # one node of 64 / 80 slots (tests/hub_meshes.py; the other hub rows: tests/test_gpu_hub_meshes.py)
+    ("fan2d_64_2", lambda: hub_meshes.fan2d(64, 2), 7, 1000.0, 0.0025),
+    ("hub3d_8_6_2", lambda: hub_meshes.hub3d(8, 6, 2), 7, 2000.0, 0.0025),
 ]
 
 

@@ -5,7 +5,9 @@ contained nodes within the range of their simplex, a node moved across several s
 a node moved out of the mesh flagged and extrapolated; the face-neighbour table; the refusals.
 
 The project's rect meshes carry cell centres: rect(2, 17) has 613 nodes and rect(3, 6) 559, so both
-span more than two 256-node blocks with a partial one."""
+span more than two 256-node blocks with a partial one.  The hub meshes (tests/hub_meshes.py) put 6 to 168
+simplices at one node: their patch search runs whole chunks of 4 with every remainder, and their own
+move "hubwalk" starts walks at that node and beside it."""
 import functools
 
 import numpy as np
@@ -13,9 +15,9 @@ import pytest
 
 import mmadmm_amd as mx
 import transfer_py
-from transfer_cases import MESHES, MOVES, centre_node, fields, linear, make_mesh, moved, unreferenced
+from transfer_cases import (ALL_MESHES, CASES, HUB_MESHES, MESHES, centre_node, fields, hubwalk_nodes, linear, make_mesh,
+                            moved, unreferenced)
 
-CASES = [(n, m) for n in MESHES for m in MOVES]
 KEYS = mx.TRANSFER_COUNTS
 
 
@@ -108,14 +110,47 @@ def test_contained_nodes_stay_in_range(name, move):
     assert (un[inside] >= lo - pad).all() and (un[inside] <= hi + pad).all()
 
 
-@pytest.mark.parametrize("name", MESHES)
+@pytest.mark.parametrize("name", ALL_MESHES)
 @pytest.mark.parametrize("move", ["a0.1", "a0.45"])
 def test_small_moves_stay_in_the_patch(name, move):
     # a = 0.1 is inside the star of every interior node (inradius >= h / sqrt(3)); at a = 0.45 the
-    # host function found every node of these meshes in its patch as well
-    _, _, _, info = host(name, move, 1)
+    # host function found every node of these meshes in its patch as well.  A hub mesh's h is its
+    # smallest altitude, and a node moved by less than that stays in its star.
+    mesh, h, F = make_mesh(name)
+    Xn, _, _, info = host(name, move, 1)
     assert info["patch"] > 0
     assert info["walked"] == 0 and info["outside"] == 0
+    if name in HUB_MESHES:  # the hub itself moved, and an independent search finds it in one of its own simplices
+        assert (Xn[0] != mesh.Xp[0]).any()
+        assert info["patch"] == int((mesh.mask == mx.INTERIOR).sum())
+        assert all((F[s] == 0).any() for s in brute_force(np.asarray(mesh.Xp), F, Xn[0]))
+
+
+@pytest.mark.parametrize("name", HUB_MESHES)
+def test_hub_walk(name):
+    """The hub moved out of its patch of 6 .. 168 simplices, and every third node of the first ring /
+    shell into a hub simplex it is no vertex of: each is walked to, lands in a simplex an independent
+    search over all simplices finds too, and the counts are that search's."""
+    mesh, h, F = make_mesh(name)
+    Xn, u, un, info = host(name, "hubwalk", 1)
+    hub, movers, n_fan = hubwalk_nodes(mesh)
+    assert n_fan == np.bincount(F.reshape(-1))[hub] and len(movers) >= 2
+    X = np.asarray(mesh.Xp)
+    want = dict.fromkeys(KEYS, 0)
+    for v in range(mesh.nP):
+        w = int(info["where"][v])
+        if (Xn[v] == X[v]).all():
+            want["copied"] += 1
+            assert w == -1
+            continue
+        assert v == hub or v in movers
+        holders = brute_force(X, F, Xn[v])
+        assert holders.size == 1, "the targets lie inside one simplex, off its faces"
+        assert not (F[holders[0]] == v).any(), "the target is outside the node's patch"
+        want["walked"] += 1
+        assert w == holders[0]
+    assert info["where"][hub] >= n_fan, "the hub leaves the simplices at the hub"
+    assert counts(info) == [want[k] for k in KEYS] == [mesh.nP - 1 - len(movers), 0, 1 + len(movers), 0]
 
 
 @pytest.mark.parametrize("name", MESHES)
@@ -160,7 +195,7 @@ def test_outside_move_is_flagged_and_extrapolated(name):
     assert abs(un[v, 0] - want) <= 1e-12 * max(1.0, np.abs(u).max()) * max(1.0, np.abs(lam).max())
 
 
-@pytest.mark.parametrize("name", MESHES)
+@pytest.mark.parametrize("name", ALL_MESHES)
 def test_face_neighbour_table(name):
     mesh, h, F = make_mesh(name)
     nbr = mx.face_neighbours(F, mesh.nP)

@@ -4,15 +4,26 @@ import functools
 
 import numpy as np
 
+import hub_meshes
 import mmadmm_amd as mx
+from field_monitor_cases import HUB_MESHES, min_altitude, static_monitor, step_params  # noqa: F401
 
 MESHES = ["rect2_5", "rect2_8", "rect2_17", "rect3_4", "rect3_6", "hexdisc6", "shoulder2_8"]
 MOVES = ["a0.1", "a0.45", "big", "outside"]
+# one high-valence hub (tests/hub_meshes.py): 6, 7, 13, 64, 100, 80 and 168 simplices at node 0, so the patch
+# search's chunks of 4 see every remainder.  Their h is the smallest altitude, so a move of a h < h stays in the
+# node's patch; "hubwalk" sends the hub and every third node of the first ring / shell out of their patches
+HUB_MOVES = ["a0.1", "a0.45", "hubwalk"]
+ALL_MESHES = MESHES + HUB_MESHES
+CASES = [(n, m) for n in MESHES for m in MOVES] + [(n, m) for n in HUB_MESHES for m in HUB_MOVES]
 
 
 @functools.lru_cache(maxsize=None)
 def make_mesh(name):
     """(mesh, h, F re-oriented as an engine holds it)"""
+    if hub_meshes.is_hub(name):
+        mesh = hub_meshes.by_name(name)
+        return mesh, min_altitude(mesh.Xp, mesh.F), mesh.F  # positively oriented as generated: held as it is
     kind, n = name.split("_") if "_" in name else (name[:-1], name[-1])
     n = int(n)
     if kind == "rect2":
@@ -30,6 +41,13 @@ def make_mesh(name):
     mx._check(mx.lib().mmadmm_mesh_reorient(mesh.dim, mesh.nP, mx._dp(X), F.shape[0], mx._ip(F)))
     F.setflags(write=False)
     return mesh, h, F
+
+
+def hubwalk_nodes(mesh):
+    """(the hub, the nodes of the first ring / shell that "hubwalk" moves: every third one)"""
+    n_fan = int((mesh.F == 0).any(axis=1).sum())
+    first = np.unique(mesh.F[:n_fan])[1:]
+    return 0, first[::3], n_fan
 
 
 def interior(mesh):
@@ -67,6 +85,19 @@ def moved(name, move, seed=4321):
         assert (X[v] > 0.0).all() and (X[v] < 1.0).all(), "the big move must stay inside the box"
     elif move == "outside":
         X[centre_node(mesh)] = OUTSIDE[D]
+    elif move == "hubwalk":
+        # the hub to a point between the first two rings / shells, off every face: outside its own patch of n_fan
+        # simplices.  Every third node of the first ring / shell to the centroid of a hub simplex it is no vertex of
+        hub, movers, n_fan = hubwalk_nodes(mesh)
+        Xo = np.asarray(mesh.Xp)
+        cen = Xo[mesh.F[:n_fan]].mean(axis=1)
+        w = np.array([0.0, 0.5, 0.3, 0.2][: D + 1])  # weights of the simplex's vertices (the hub's own: none)
+        w = w / w.sum()
+        X[hub] = Xo[hub] + 1.5 * ((w[:, None] * Xo[mesh.F[1]]).sum(axis=0) - Xo[hub])
+        for v in movers:  # (the nearest such simplex: a short walk, well under the walk's limit of moves)
+            d = ((cen - Xo[v]) ** 2).sum(axis=1)
+            d[(mesh.F[:n_fan] == v).any(axis=1)] = np.inf
+            X[v] = cen[np.argmin(d)]
     else:
         raise KeyError(move)
     return X
