@@ -158,6 +158,34 @@ int mmadmm_get_device(mmadmm_handle h, const char* what, double* d_out, void* co
 int mmadmm_field_monitor(int dim, int nP, const double* Xp, int nF, const int32_t* F, const double* u,
                          double alpha, double* H, double* M);
 
+/* Huang's normalised monitor of the field, for linear interpolation error:
+ *   M_v = det(I + |H_v| / alpha)^(-1/(D+4)) (I + |H_v| / alpha),
+ * so the mesh density rho_v = sqrt(det M_v) = det(I + |H_v| / alpha)^(2/(D+4)).  The root is a fixed
+ * Newton iteration in + - * / (within 1 ulp measured; the same bits on the device, the host and in
+ * tests/field_huang_py.py).  alpha > 0 and finite: that alpha.  alpha == 0.0: alpha is solved on the
+ * device from the equidistribution equation
+ *   sum_v omega_v rho_v(alpha) = 2 sum_v omega_v,   omega_v = (volume of v's simplices) / (D + 1),
+ * about half of the density going to the curved regions whatever the field's scale: halving from
+ * Lambda (the largest |eigenvalue| of any H_v) until the sum exceeds the right-hand side, then
+ * bisection to neighbouring doubles, the sums in a fixed tree order (bitwise reproducible).  A field
+ * with H = 0 everywhere (or a mesh of no volume) has no root: alpha = 1.0, M = I.  Any other alpha
+ * (negative, NaN, infinite) is MMADMM_ERR_INVALID.  alpha_used (host pointer, may be NULL) receives
+ * the alpha the monitor was built with.  A given alpha adds no synchronisation to the rebuild; a
+ * solved one reads a 56-byte record back once per 64 evaluated sums (about 60 are typical: one
+ * read-back).  Otherwise as mmadmm_regrid_field(_device): the same rebuild, single rank only, the same
+ * event ordering on producer_stream.  mmadmm_field_solve_info: the sums evaluated and the read-backs
+ * of the engine's last solve (0, 0 after a given alpha); either pointer may be NULL.
+ * mmadmm_field_monitor_huang is the host-only twin (no device): H and / or M (nP x D*D) may be NULL,
+ * bit-identical to the device calls, alpha as above.  mmadmm_field_root (a test hook): out[i] = the
+ * n-th root (n = 3 or 7) of d[i] >= 1 by that Newton iteration. */
+int mmadmm_regrid_field_huang(mmadmm_handle h, const double* u, double alpha, double* alpha_used);
+int mmadmm_regrid_field_huang_device(mmadmm_handle h, const double* d_u, double alpha, void* producer_stream,
+                                     double* alpha_used);
+int mmadmm_field_solve_info(mmadmm_handle h, int* passes, int* syncs);
+int mmadmm_field_monitor_huang(int dim, int nP, const double* Xp, int nF, const int32_t* F, const double* u,
+                               double alpha, double* alpha_used, double* H, double* M);
+int mmadmm_field_root(int n, int count, const double* d, double* out);
+
 /* ---- nodal fields onto the moved mesh (no reference counterpart)
  * After mmadmm_step the nodes have moved and u[v] still holds the caller's field at the old position
  * of node v.  mmadmm_transfer evaluates the piecewise-linear field (old positions Xold, nP x D;

@@ -95,6 +95,15 @@ public:
         mmadmm_cxx::check(onDevice ? mmadmm_regrid_field_device(h_, u, alpha, nullptr)
                                    : mmadmm_regrid_field(h_, u, alpha));
     }
+    // Huang's normalised monitor M = det(I + |H| / alpha)^(-1/(D+4)) (I + |H| / alpha) of the field u;
+    // alpha 0: solved on the device from the equidistribution equation.  Returns the alpha used, to
+    // be passed to later calls (include/mmadmm.h: mmadmm_regrid_field_huang and its _device form)
+    double regridFromFieldHuang(const double *u, double alpha = 0.0, bool onDevice = false) {
+        double used = 0.0;
+        mmadmm_cxx::check(onDevice ? mmadmm_regrid_field_huang_device(h_, u, alpha, nullptr, &used)
+                                   : mmadmm_regrid_field_huang(h_, u, alpha, &used));
+        return used;
+    }
     // the caller's nodal field (C components per node, nP x C row-major) carried from the node
     // positions Xold (nP x D row-major, e.g. those before step()) to the current ones, piecewise
     // linearly on the old mesh (no reference counterpart; include/mmadmm.h: mmadmm_transfer and

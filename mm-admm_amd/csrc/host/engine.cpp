@@ -63,6 +63,9 @@ struct EngineBase {
   // mmadmm_get_device): src = kMonValues (nP x D*D tensors) or kMonField (nP values of a scalar field)
   virtual void regridFrom(int src, const double* p, bool onDevice, double alpha, void* stream) = 0;
   virtual void fieldHessian(const double* u, double* H, bool onDevice, void* stream) = 0;
+  // the alpha of the last regridFrom(kMonFieldHuang, ...): the given one, or the one solved
+  virtual double fieldAlphaUsed() const = 0;
+  virtual void fieldSolveInfo(int* passes, int* syncs) const = 0;
   virtual void getDevice(const std::string& what, double* dOut, void* stream) = 0;
   // mmadmm_transfer(_device): nodal fields from the old node positions to the new ones (Xnew null: Vp)
   virtual void transfer(const double* Xold, const double* Xnew, int C, const double* uold, double* unew, int32_t* where,
@@ -74,7 +77,7 @@ struct EngineBase {
 // Mesh::reOrientElements (src/Mesh.cpp:243-260): swap F(i,1), F(i,2) when det(E) < 0, E the
 // edge vectors from vertex 0 as columns, Eigen's 2x2 / 3x3 determinant
 // the source of the monitor at the vertices of a grid rebuild (regridAll)
-enum MonSource { kMonBuiltin7 = 0, kMonCallback = 1, kMonValues = 2, kMonField = 3 };
+enum MonSource { kMonBuiltin7 = 0, kMonCallback = 1, kMonValues = 2, kMonField = 3, kMonFieldHuang = 4 };
 
 void reorient_simplices(int D, const double* Vp, int nF, int32_t* F) {
   for (int s = 0; s < nF; ++s) {
@@ -327,6 +330,7 @@ class Engine final : public EngineBase {
 
   ~Engine() override {
     if (rgHost_) (void)hipHostFree(rgHost_);
+    if (fldStH_) (void)hipHostFree(fldStH_);
     if (rgnHost_) (void)hipHostFree(rgnHost_);
     if (jac_) (void)mmx_matrix_destroy(jac_);
     for (auto& e : evPool_) (void)hipEventDestroy(e);
@@ -1066,12 +1070,53 @@ class Engine final : public EngineBase {
     fldE_.alloc(std::max<size_t>(field_ebuf_doubles<D>(nF_), 1));
     fldG_.alloc((size_t)nP_ * D);
   }
+  // Huang's monitor: |H|, {l, omega}, the partial sums of a pass, the search's state record and its
+  // pinned host copy
+  void huangScratch() {
+    if (fldA_.p) return;
+    fldA_.alloc((size_t)nP_ * D * D);
+    fldL_.alloc((size_t)nP_ * (D + 1));
+    fldPart_.alloc((size_t)2 * field_solve_blocks(nP_));
+    fldSt_.alloc(1);
+    MMX_HIP(hipHostMalloc((void**)&fldStH_, sizeof(FieldSolve), hipHostMallocDefault));
+  }
+  // Huang's monitor of the field srcPtr_ at the positions X into rgMon_: recovery, alpha given
+  // (srcAlpha_ > 0) or solved (0) in batches of kFieldBatch (sum, update) kernel pairs with one
+  // read-back of the state record per batch, final pass.  A given alpha synchronises nowhere.
+  void fieldHuangMonitor(const double* X) {
+    fieldScratch();
+    huangScratch();
+    launch_field_huang_recover<D>(X, srcPtr_, F_.p, nF_, incPtr_.p, incOff_.p, nodeOrder_.p, nP_, fldE_.p, fldG_.p,
+                                  fldA_.p, fldL_.p, st_);
+    launch_field_solve_set(fldSt_.p, srcAlpha_, st_);
+    fldAlphaUsed_ = srcAlpha_;
+    fldPasses_ = fldSyncs_ = 0;
+    if (!(srcAlpha_ > 0.0)) {
+      do {
+        launch_field_solve_passes<D>(fldL_.p, nP_, fldSt_.p, fldPart_.p, kFieldBatch, st_);
+        MMX_HIP(hipGetLastError());
+        MMX_HIP(hipMemcpyAsync(fldStH_, fldSt_.p, sizeof(FieldSolve), hipMemcpyDeviceToHost, st_));
+        streamWait();
+        fldSyncs_++;
+      } while (fldStH_->phase != kFieldDone);
+      fldAlphaUsed_ = fldStH_->alpha;
+      fldPasses_ = fldStH_->passes;
+    }
+    launch_field_huang_final<D>(fldA_.p, fldL_.p, nP_, fldSt_.p, rgMon_.p, st_);
+  }
+  double fieldAlphaUsed() const override { return fldAlphaUsed_; }
+  void fieldSolveInfo(int* passes, int* syncs) const override {
+    if (passes) *passes = fldPasses_;
+    if (syncs) *syncs = fldSyncs_;
+  }
 
   // mmadmm_regrid_values / mmadmm_regrid_field (and their _device forms): the rebuild of regridAll
   // from the caller's monitor tensors, or from the monitor recovered from the caller's nodal field
   void regridFrom(int src, const double* p, bool onDevice, double alpha, void* stream) override {
-    singleRankOnly(src == kMonField ? "mmadmm_regrid_field" : "mmadmm_regrid_values");
-    const size_t n = (size_t)nP_ * (src == kMonField ? 1 : D * D);
+    singleRankOnly(src == kMonFieldHuang ? "mmadmm_regrid_field_huang"
+                   : src == kMonField    ? "mmadmm_regrid_field"
+                                         : "mmadmm_regrid_values");
+    const size_t n = (size_t)nP_ * (src == kMonValues ? D * D : 1);
     if (!onDevice) {  // staged: the host array is copied before the call returns
       if (fldIn_.n < n) fldIn_.alloc(n);
       MMX_HIP(hipMemcpyAsync(fldIn_.p, p, n * sizeof(double), hipMemcpyHostToDevice, st_));
@@ -1553,6 +1598,8 @@ class Engine final : public EngineBase {
       fieldScratch();
       launch_field_hessian<D>(X, srcPtr_, F_.p, nF_, incPtr_.p, incOff_.p, nodeOrder_.p, nP_, fldE_.p, fldG_.p,
                               srcAlpha_, nullptr, rgMon_.p, st_);
+    } else if (src == kMonFieldHuang) {
+      fieldHuangMonitor(X);
     } else if (src == kMonBuiltin7) {
       double c[3];
       moving_bump_centre(t, c);
@@ -1773,6 +1820,14 @@ class Engine final : public EngineBase {
   // the monitor from the caller's arrays (regridFrom): the element buffer and nodal gradient of the
   // recovery, staged host input / output, the source of the rebuild in flight, the caller-stream events
   DevBuf<double> fldE_, fldG_, fldIn_, fldOut_;
+  // Huang's monitor (fieldHuangMonitor): |H|, {l, omega}, a pass's partials, the search's state record
+  // (device, pinned host copy), and of the last call the alpha used, passes and read-backs
+  static constexpr int kFieldBatch = 64;
+  DevBuf<double> fldA_, fldL_, fldPart_;
+  DevBuf<FieldSolve> fldSt_;
+  FieldSolve* fldStH_ = nullptr;
+  double fldAlphaUsed_ = 1.0;
+  int fldPasses_ = 0, fldSyncs_ = 0;
   std::vector<int32_t> trNbrH_;  // the transfer's face-neighbour table (host copy) and device scratch
   DevBuf<int32_t> trNbr_, trWhere_, trCnt_;
   DevBuf<double> trStage_;
@@ -2072,6 +2127,30 @@ int mmadmm_regrid_field_device(mmadmm_handle h, const double* d_u, double alpha,
     check_alpha("mmadmm_regrid_field_device", alpha);
     eng(h).regridFrom(mmx::kMonField, d_u, true, alpha, producer_stream);
   });
+}
+static void check_alpha_huang(const char* who, double alpha) {
+  if (!(std::isfinite(alpha) && alpha >= 0))
+    throw Error(MMADMM_ERR_INVALID, std::string(who) + ": alpha must be finite and > 0, or 0 (solved)");
+}
+int mmadmm_regrid_field_huang(mmadmm_handle h, const double* u, double alpha, double* alpha_used) {
+  return guarded([&] {
+    if (!u) throw Error(MMADMM_ERR_INVALID, "mmadmm_regrid_field_huang: u is NULL");
+    check_alpha_huang("mmadmm_regrid_field_huang", alpha);
+    eng(h).regridFrom(mmx::kMonFieldHuang, u, false, alpha, nullptr);
+    if (alpha_used) *alpha_used = eng(h).fieldAlphaUsed();
+  });
+}
+int mmadmm_regrid_field_huang_device(mmadmm_handle h, const double* d_u, double alpha, void* producer_stream,
+                                     double* alpha_used) {
+  return guarded([&] {
+    if (!d_u) throw Error(MMADMM_ERR_INVALID, "mmadmm_regrid_field_huang_device: d_u is NULL");
+    check_alpha_huang("mmadmm_regrid_field_huang_device", alpha);
+    eng(h).regridFrom(mmx::kMonFieldHuang, d_u, true, alpha, producer_stream);
+    if (alpha_used) *alpha_used = eng(h).fieldAlphaUsed();
+  });
+}
+int mmadmm_field_solve_info(mmadmm_handle h, int* passes, int* syncs) {
+  return guarded([&] { eng(h).fieldSolveInfo(passes, syncs); });
 }
 int mmadmm_field_hessian(mmadmm_handle h, const double* u, double* H) {
   return guarded([&] {

@@ -1,7 +1,8 @@
-// field_monitor.cpp -- mmadmm_field_monitor: the Hessian-recovered monitor of a nodal scalar field
-// on the host (no device needed), compiled from the very text the device kernels run
-// (kernels/field_math.h; DESIGN.md §Monitor from a nodal field): bit-identical to
-// mmadmm_field_hessian / mmadmm_regrid_field at the same positions and simplices.
+// field_monitor.cpp -- mmadmm_field_monitor and mmadmm_field_monitor_huang: the Hessian-recovered
+// monitor of a nodal scalar field on the host (no device needed), compiled from the very text the
+// device kernels run (kernels/field_math.h; DESIGN.md §Monitor from a nodal field): bit-identical to
+// mmadmm_field_hessian / mmadmm_regrid_field / mmadmm_regrid_field_huang at the same positions and
+// simplices.
 #include <cmath>
 #include <vector>
 
@@ -11,9 +12,10 @@
 namespace mmx {
 namespace {
 
-template <int D>
-void field_monitor_host(int nP, const double* X, int nF, const int32_t* F, const double* u, double alpha, double* H,
-                        double* M) {
+// the two recoveries; node(v, G, sw) receives the second one (G, D x D) and the node's sum of
+// simplex weights, v ascending
+template <int D, class NodeFn>
+void field_recover_host(int nP, const double* X, int nF, const int32_t* F, const double* u, NodeFn node) {
   constexpr int K = D * (D + 1), DD = D * D;
   // node -> incident slot offsets s K + n D in ascending simplex id (the engine's incidence CSR)
   std::vector<int> ptr((size_t)nP + 1, 0), off((size_t)nF * (D + 1));
@@ -35,10 +37,80 @@ void field_monitor_host(int nP, const double* X, int nF, const int32_t* F, const
     field_element<D, D>(X, grad.data(), f, &ebuf[(size_t)s * (1 + DD)]);
   }
   for (int v = 0; v < nP; ++v) {
-    double G[DD];
-    field_node<D, D>(off.data() + ptr[v], ptr[v + 1] - ptr[v], ebuf.data(), G);
-    field_epilogue<D>(G, alpha, H ? H + (size_t)v * DD : nullptr, M ? M + (size_t)v * DD : nullptr);
+    double G[DD], sw;
+    field_node<D, D>(off.data() + ptr[v], ptr[v + 1] - ptr[v], ebuf.data(), G, &sw);
+    node(v, G, sw);
   }
+}
+
+template <int D>
+void field_monitor_host(int nP, const double* X, int nF, const int32_t* F, const double* u, double alpha, double* H,
+                        double* M) {
+  constexpr int DD = D * D;
+  field_recover_host<D>(nP, X, nF, F, u, [&](int v, const double* G, double) {
+    field_epilogue<D>(G, alpha, H ? H + (size_t)v * DD : nullptr, M ? M + (size_t)v * DD : nullptr);
+  });
+}
+
+// the device's fixed-shape sum (kernels/block_reduce.h) on the host: block_sum's tree over 256 lanes,
+// and fin_sum over the per-block partials
+constexpr int kRB = 256;
+double tree_sum(double* red) {
+  for (int w = kRB / 2; w > 0; w >>= 1)
+    for (int t = 0; t < w; ++t) red[t] = red[t] + red[t + w];
+  return red[0];
+}
+double fin_sum_host(const std::vector<double>& part) {
+  double red[kRB];
+  for (int t = 0; t < kRB; ++t) {
+    double v = 0.0;
+    for (size_t b = t; b < part.size(); b += kRB) v += part[b];
+    red[t] = v;
+  }
+  return tree_sum(red);
+}
+// R(value(v)) over the node ids: each block 256 consecutive ids, missing lanes 0.0
+template <class ValueFn>
+double field_sum_host(int nP, ValueFn value) {
+  std::vector<double> part((size_t)(nP + kRB - 1) / kRB);
+  for (size_t b = 0; b < part.size(); ++b) {
+    double red[kRB];
+    for (int t = 0; t < kRB; ++t) {
+      const long long v = (long long)b * kRB + t;
+      red[t] = v < nP ? value((int)v) : 0.0;
+    }
+    part[b] = tree_sum(red);
+  }
+  return fin_sum_host(part);
+}
+
+template <int D>
+double field_monitor_huang_host(int nP, const double* X, int nF, const int32_t* F, const double* u, double alpha,
+                                double* H, double* M) {
+  constexpr int DD = D * D;
+  std::vector<double> A((size_t)nP * DD), l((size_t)nP * D), om(nP);
+  field_recover_host<D>(nP, X, nF, F, u, [&](int v, const double* G, double sw) {
+    field_huang_node<D>(G, sw, H ? H + (size_t)v * DD : nullptr, &A[(size_t)v * DD], &l[(size_t)v * D], &om[v]);
+  });
+  if (!(alpha > 0.0)) {  // the device's search (field_math.h: field_solve_*), sum by sum
+    double Lambda = 0.0;
+    for (size_t i = 0; i < l.size(); ++i) Lambda = l[i] > Lambda ? l[i] : Lambda;
+    FieldSolve st{};
+    field_solve_begin(&st, field_sum_host(nP, [&](int v) { return om[v]; }), Lambda);
+    while (st.phase != kFieldDone)
+      field_solve_advance(&st, field_sum_host(nP, [&](int v) {
+                            return om[v] * field_huang_rho<D>(&l[(size_t)v * D], st.trial, nullptr);
+                          }));
+    alpha = st.alpha;
+  }
+  if (M)
+    for (int v = 0; v < nP; ++v) field_huang_monitor<D>(&A[(size_t)v * DD], &l[(size_t)v * D], alpha, M + (size_t)v * DD);
+  return alpha;
+}
+
+void check_field_arrays(const char* who, int dim, int nP, const double* Xp, int nF, const int32_t* F, const double* u) {
+  if ((dim != 2 && dim != 3) || nP < 1 || nF < 0) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": bad dim / sizes");
+  if (!Xp || !u || (nF > 0 && !F)) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": NULL array");
 }
 
 }  // namespace
@@ -47,9 +119,7 @@ void field_monitor_host(int nP, const double* X, int nF, const int32_t* F, const
 extern "C" int mmadmm_field_monitor(int dim, int nP, const double* Xp, int nF, const int32_t* F, const double* u,
                                     double alpha, double* H, double* M) {
   return mmx::guarded([&] {
-    if ((dim != 2 && dim != 3) || nP < 1 || nF < 0)
-      throw mmx::Error(MMADMM_ERR_INVALID, "mmadmm_field_monitor: bad dim / sizes");
-    if (!Xp || !u || (nF > 0 && !F)) throw mmx::Error(MMADMM_ERR_INVALID, "mmadmm_field_monitor: NULL array");
+    mmx::check_field_arrays("mmadmm_field_monitor", dim, nP, Xp, nF, F, u);
     if (M && !(std::isfinite(alpha) && alpha > 0))
       throw mmx::Error(MMADMM_ERR_INVALID, "mmadmm_field_monitor: alpha must be finite and > 0");
     for (long long i = 0; i < (long long)nF * (dim + 1); ++i)
@@ -58,5 +128,27 @@ extern "C" int mmadmm_field_monitor(int dim, int nP, const double* Xp, int nF, c
       mmx::field_monitor_host<2>(nP, Xp, nF, F, u, alpha, H, M);
     else
       mmx::field_monitor_host<3>(nP, Xp, nF, F, u, alpha, H, M);
+  });
+}
+
+extern "C" int mmadmm_field_monitor_huang(int dim, int nP, const double* Xp, int nF, const int32_t* F,
+                                          const double* u, double alpha, double* alpha_used, double* H, double* M) {
+  return mmx::guarded([&] {
+    mmx::check_field_arrays("mmadmm_field_monitor_huang", dim, nP, Xp, nF, F, u);
+    if (!(std::isfinite(alpha) && alpha >= 0))
+      throw mmx::Error(MMADMM_ERR_INVALID, "mmadmm_field_monitor_huang: alpha must be finite and > 0, or 0 (solved)");
+    for (long long i = 0; i < (long long)nF * (dim + 1); ++i)
+      if (F[i] < 0 || F[i] >= nP) throw mmx::Error(MMADMM_ERR_INVALID, "simplex vertex id out of range");
+    const double a = dim == 2 ? mmx::field_monitor_huang_host<2>(nP, Xp, nF, F, u, alpha, H, M)
+                              : mmx::field_monitor_huang_host<3>(nP, Xp, nF, F, u, alpha, H, M);
+    if (alpha_used) *alpha_used = a;
+  });
+}
+
+extern "C" int mmadmm_field_root(int n, int count, const double* d, double* out) {
+  return mmx::guarded([&] {
+    if ((n != 3 && n != 7) || count < 0 || (count > 0 && (!d || !out)))
+      throw mmx::Error(MMADMM_ERR_INVALID, "mmadmm_field_root: n is 3 or 7, d and out hold count values");
+    for (int i = 0; i < count; ++i) out[i] = n == 3 ? mmx::field_root<3>(d[i]) : mmx::field_root<7>(d[i]);
   });
 }

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "field_math.h"
+
 namespace mmx {
 
 // doubles of the element buffer (nF x {w, g[D][D]}) and of the nodal gradient (nP x D)
@@ -21,5 +23,23 @@ template <int D>
 void launch_field_hessian(const double* X, const double* u, const int* F, int nF, const int* incPtr, const int* incOff,
                           const int* nodeOrder, int nP, double* ebuf, double* grad, double alpha, double* H, double* M,
                           hipStream_t st);
+
+// Huang's normalised monitor M = (I + |H| / alpha) / t (field_math.h).  The same two element + node
+// passes, the last one storing absH (|H|, nP x D*D) and lw ({l_0 .. l_{D-1}, omega} component-major,
+// (D + 1) x nP) instead of M; then the state record is set (alpha > 0: given; 0: to be solved), the
+// search advanced by `passes` (sum, update) kernel pairs at a time -- the caller reads the record
+// back between batches and stops at phase == kFieldDone; pairs past that do nothing -- and the
+// final pass writes M (nP x D*D) with the record's alpha.  part: 2 field_solve_blocks(nP) doubles.
+inline int field_solve_blocks(int nP) { return (nP + 255) / 256; }
+template <int D>
+void launch_field_huang_recover(const double* X, const double* u, const int* F, int nF, const int* incPtr,
+                                const int* incOff, const int* nodeOrder, int nP, double* ebuf, double* grad,
+                                double* absH, double* lw, hipStream_t st);
+void launch_field_solve_set(FieldSolve* state, double alpha, hipStream_t st);
+template <int D>
+void launch_field_solve_passes(const double* lw, int nP, FieldSolve* state, double* part, int passes, hipStream_t st);
+template <int D>
+void launch_field_huang_final(const double* absH, const double* lw, int nP, const FieldSolve* state, double* M,
+                              hipStream_t st);
 
 }  // namespace mmx

@@ -7,8 +7,13 @@
 //                 neighbouring simplices): walks the node's incidence list in ascending simplex id
 //                 and sums the element rows -- every contribution stored once with plain stores
 //                 and summed per destination in a fixed order: no atomics, bitwise reproducible
+// Huang's normalised monitor: the last node pass stores |H|, the Jacobi diagonal l
+// and omega per node instead of M; alpha is given, or solved on the device by (k_field_sigma,
+// k_field_update) pairs -- the partial sums change hands at the kernel boundary, the state record
+// of the search (FieldSolve) lives in device memory -- and a final pass writes M.
 #include <hip/hip_runtime.h>
 
+#include "block_reduce.h"
 #include "field_kernels.h"
 #include "field_math.h"
 
@@ -51,6 +56,127 @@ __global__ void __launch_bounds__(kFB) k_field_node(const int* __restrict__ incP
   }
 }
 
+// the epilogue of Huang's monitor: |H| (nP x D*D), and lw = {l_0 .. l_{D-1}, omega}, each nP
+// values, component-major (the sums of k_field_sigma stream them by natural node id)
+template <int D>
+__global__ void __launch_bounds__(kFB) k_field_node_huang(const int* __restrict__ incPtr,
+                                                          const int* __restrict__ incOff,
+                                                          const int* __restrict__ nodeOrder, int nP,
+                                                          const double* __restrict__ ebuf, double* __restrict__ absH,
+                                                          double* __restrict__ lw) {
+  const int idx = blockIdx.x * kFB + threadIdx.x;
+  if (idx >= nP) return;
+  const int v = nodeOrder[idx];
+  const int b = incPtr[v], e = incPtr[v + 1];
+  double r[D * D], sw, A[D * D], l[D], om;
+  field_node<D, D>(incOff + b, e - b, ebuf, r, &sw);
+  field_huang_node<D>(r, sw, nullptr, A, l, &om);
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) absH[(size_t)v * D * D + i] = A[i];
+#pragma unroll
+  for (int k = 0; k < D; ++k) lw[(size_t)k * nP + v] = l[k];
+  lw[(size_t)D * nP + v] = om;
+}
+
+// the state of the search before its first pass; alpha > 0: nothing to solve
+__global__ void k_field_solve_set(FieldSolve* st, double alpha) {
+  FieldSolve s;
+  s.lo = s.hi = s.trial = s.twoOmega = s.lambda = 0.0;
+  s.alpha = alpha;
+  s.phase = alpha > 0.0 ? kFieldDone : kFieldInit;
+  s.passes = 0;
+  *st = s;
+}
+
+// one pass of the search: workgroup b sums omega_v rho_v(trial) over the node ids 256 b .. 256 b + 255
+// (missing lanes 0.0) by the block tree into part[b].  The first pass (kFieldInit) sums omega_v
+// alone and takes the largest l into part[nblk + b].  Nothing once the search is done.
+template <int D>
+__global__ void __launch_bounds__(kFB) k_field_sigma(const double* __restrict__ lw, int nP, const FieldSolve* st,
+                                                     double* __restrict__ part) {
+  __shared__ double red[kFB][1];
+  const int phase = st->phase;
+  if (phase == kFieldDone) return;
+  const double trial = st->trial;
+  const int v = blockIdx.x * kFB + threadIdx.x;
+  double val[1] = {0.0};
+  double mx = 0.0;
+  if (v < nP) {
+    double l[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) l[k] = lw[(size_t)k * nP + v];
+    const double om = lw[(size_t)D * nP + v];
+    if (phase == kFieldInit) {
+      val[0] = om;
+#pragma unroll
+      for (int k = 0; k < D; ++k) mx = l[k] > mx ? l[k] : mx;
+    } else {
+      val[0] = om * field_huang_rho<D>(l, trial, nullptr);
+    }
+  }
+  block_sum<1, kFB>(val, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = val[0];
+  if (phase != kFieldInit) return;
+  __syncthreads();  // every lane has read red[0]
+  red[threadIdx.x][0] = mx;
+  __syncthreads();
+  for (int w = kFB / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      const double o = red[threadIdx.x + w][0];
+      if (o > red[threadIdx.x][0]) red[threadIdx.x][0] = o;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[gridDim.x + blockIdx.x] = red[0][0];
+}
+
+// one workgroup: the pass's sum by fin_sum, then the state record advanced (field_math.h)
+__global__ void __launch_bounds__(kFB) k_field_update(FieldSolve* st, const double* __restrict__ part, int nblk) {
+  __shared__ double red[kFB][1];
+  const int phase = st->phase;
+  if (phase == kFieldDone) return;
+  const double sum = fin_sum<kFB>(part, nblk, red);
+  if (phase == kFieldInit) {
+    double mx = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += kFB) mx = part[nblk + b] > mx ? part[nblk + b] : mx;
+    red[threadIdx.x][0] = mx;
+    __syncthreads();
+    for (int w = kFB / 2; w > 0; w >>= 1) {
+      if ((int)threadIdx.x < w) {
+        const double o = red[threadIdx.x + w][0];
+        if (o > red[threadIdx.x][0]) red[threadIdx.x][0] = o;
+      }
+      __syncthreads();
+    }
+  }
+  if (threadIdx.x == 0) {
+    FieldSolve s = *st;
+    if (phase == kFieldInit)
+      field_solve_begin(&s, sum, red[0][0]);
+    else
+      field_solve_advance(&s, sum);
+    *st = s;
+  }
+}
+
+// M = (I + |H| / alpha) / t per node, alpha from the state record
+template <int D>
+__global__ void __launch_bounds__(kFB) k_field_huang_final(const double* __restrict__ absH,
+                                                           const double* __restrict__ lw, int nP,
+                                                           const FieldSolve* __restrict__ st, double* __restrict__ M) {
+  const int v = blockIdx.x * kFB + threadIdx.x;
+  if (v >= nP) return;
+  const double alpha = st->alpha;
+  double A[D * D], l[D], m[D * D];
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) A[i] = absH[(size_t)v * D * D + i];
+#pragma unroll
+  for (int k = 0; k < D; ++k) l[k] = lw[(size_t)k * nP + v];
+  field_huang_monitor<D>(A, l, alpha, m);
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) M[(size_t)v * D * D + i] = m[i];
+}
+
 }  // namespace
 
 template <int D>
@@ -70,5 +196,47 @@ template void launch_field_hessian<2>(const double*, const double*, const int*, 
                                       int, double*, double*, double, double*, double*, hipStream_t);
 template void launch_field_hessian<3>(const double*, const double*, const int*, int, const int*, const int*, const int*,
                                       int, double*, double*, double, double*, double*, hipStream_t);
+
+template <int D>
+void launch_field_huang_recover(const double* X, const double* u, const int* F, int nF, const int* incPtr,
+                                const int* incOff, const int* nodeOrder, int nP, double* ebuf, double* grad,
+                                double* absH, double* lw, hipStream_t st) {
+  if (nF < 1 || nP < 1) return;
+  hipLaunchKernelGGL((k_field_elem<D, 1>), dim3(fblocks(nF)), dim3(kFB), 0, st, X, u, F, nF, ebuf);
+  hipLaunchKernelGGL((k_field_node<D, 1>), dim3(fblocks(nP)), dim3(kFB), 0, st, incPtr, incOff, nodeOrder, nP, ebuf,
+                     grad, 1.0, (double*)nullptr, (double*)nullptr);
+  hipLaunchKernelGGL((k_field_elem<D, D>), dim3(fblocks(nF)), dim3(kFB), 0, st, X, grad, F, nF, ebuf);
+  hipLaunchKernelGGL((k_field_node_huang<D>), dim3(fblocks(nP)), dim3(kFB), 0, st, incPtr, incOff, nodeOrder, nP, ebuf,
+                     absH, lw);
+}
+
+void launch_field_solve_set(FieldSolve* state, double alpha, hipStream_t st) {
+  hipLaunchKernelGGL(k_field_solve_set, dim3(1), dim3(1), 0, st, state, alpha);
+}
+
+template <int D>
+void launch_field_solve_passes(const double* lw, int nP, FieldSolve* state, double* part, int passes, hipStream_t st) {
+  const int nblk = field_solve_blocks(nP);
+  for (int i = 0; i < passes; ++i) {
+    hipLaunchKernelGGL((k_field_sigma<D>), dim3(nblk), dim3(kFB), 0, st, lw, nP, (const FieldSolve*)state, part);
+    hipLaunchKernelGGL(k_field_update, dim3(1), dim3(kFB), 0, st, state, (const double*)part, nblk);
+  }
+}
+
+template <int D>
+void launch_field_huang_final(const double* absH, const double* lw, int nP, const FieldSolve* state, double* M,
+                              hipStream_t st) {
+  if (nP < 1) return;
+  hipLaunchKernelGGL((k_field_huang_final<D>), dim3(fblocks(nP)), dim3(kFB), 0, st, absH, lw, nP, state, M);
+}
+
+#define MMX_FIELD_HUANG(D)                                                                                          \
+  template void launch_field_huang_recover<D>(const double*, const double*, const int*, int, const int*, const int*, \
+                                              const int*, int, double*, double*, double*, double*, hipStream_t);    \
+  template void launch_field_solve_passes<D>(const double*, int, FieldSolve*, double*, int, hipStream_t);           \
+  template void launch_field_huang_final<D>(const double*, const double*, int, const FieldSolve*, double*, hipStream_t);
+MMX_FIELD_HUANG(2)
+MMX_FIELD_HUANG(3)
+#undef MMX_FIELD_HUANG
 
 }  // namespace mmx

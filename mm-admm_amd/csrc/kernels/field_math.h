@@ -12,6 +12,11 @@
 //   |H|       cyclic Jacobi with Rutishauser's rotation (2D: one; 3D: kFieldSweeps sweeps over
 //             (0,1), (0,2), (1,2)), |H|_ij = sum_k (V_ik |lambda_k|) V_jk left to right, j >= i, mirrored
 //   monitor   M_ij = delta_ij + |H|_ij / alpha
+//   Huang     the normalised form (Huang's metric): l_k = |a_kk| the Jacobi diagonal,
+//             d = ((1 + l_0 / alpha) (1 + l_1 / alpha)) [(1 + l_2 / alpha)]; 2D: c = root3(d), rho = c,
+//             t = sqrt(c); 3D: s = root7(d), rho = s s, t = s; M_ij = (delta_ij + |H|_ij / alpha) / t, so
+//             sqrt(det M) = rho; omega_v = (sum_s w_s) / (D + 1); alpha given, or solved from
+//             sum_v omega_v rho_v(alpha) = 2 sum_v omega_v (field_solve_*)
 #pragma once
 
 #if defined(__HIPCC__)
@@ -114,7 +119,7 @@ MMX_FHD void field_store_row(const double* row, double* eb) {
 }
 
 template <int D, int C>
-MMX_FHD void field_node(const int* off, int cnt, const double* ebuf, double* r) {
+MMX_FHD void field_node(const int* off, int cnt, const double* ebuf, double* r, double* swOut = nullptr) {
   constexpr int K = D * (D + 1), S = 1 + C * D;
   double sw = 0.0;
 #pragma unroll
@@ -143,6 +148,7 @@ MMX_FHD void field_node(const int* off, int cnt, const double* ebuf, double* r) 
   }
 #pragma unroll
   for (int i = 0; i < C * D; ++i) r[i] = (sw == 0.0) ? 0.0 : r[i] / sw;
+  if (swOut) *swOut = sw;
 }
 
 // H_ij = 0.5 (G_ij + G_ji), G row-major (G_ij = d_j g_i)
@@ -185,9 +191,9 @@ MMX_FHD void field_rotate(double* a, double* v, int p, int q) {
   }
 }
 
-// |H| of the symmetric H
+// |H| of the symmetric H; l (may be null): |a_kk|, the absolute Jacobi diagonal it is assembled from
 template <int D>
-MMX_FHD void field_abs_sym(const double* H, double* A) {
+MMX_FHD void field_abs_sym(const double* H, double* A, double* l = nullptr) {
   double a[D * D], v[D * D];
 #pragma unroll
   for (int i = 0; i < D * D; ++i) {
@@ -213,6 +219,10 @@ MMX_FHD void field_abs_sym(const double* H, double* A) {
       A[i * D + j] = s;
       A[j * D + i] = s;
     }
+  if (l) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) l[k] = field_abs(a[k * D + k]);
+  }
 }
 
 // the node epilogue: G (the second recovery, D x D) -> H and/or M = I + |H| / alpha (either may be null)
@@ -228,6 +238,177 @@ MMX_FHD void field_epilogue(const double* G, double alpha, double* H, double* M)
     field_abs_sym<D>(h, ab);
 #pragma unroll
     for (int i = 0; i < D * D; ++i) M[i] = ((i / D == i % D) ? 1.0 : 0.0) + ab[i] / alpha;
+  }
+}
+
+// ---- Huang's normalised monitor ----------------------------------------------------------------
+
+constexpr double kFieldMaxDouble = 1.7976931348623157e308;
+constexpr double kFieldMinNormal = 2.2250738585072014e-308;
+
+// exact scaling by powers of two: d = m 2^e with m in [1, 2) (d finite, normal, > 0), and 2^q for
+// -1022 <= q <= 1023
+MMX_FHD double field_split(double d, int* e) {
+  unsigned long long b;
+  __builtin_memcpy(&b, &d, 8);
+  *e = (int)((b >> 52) & 0x7ffULL) - 1023;
+  b = (b & 0x000fffffffffffffULL) | 0x3ff0000000000000ULL;
+  double m;
+  __builtin_memcpy(&m, &b, 8);
+  return m;
+}
+MMX_FHD double field_pow2(int q) {
+  const unsigned long long b = (unsigned long long)(1023 + q) << 52;
+  double p;
+  __builtin_memcpy(&p, &b, 8);
+  return p;
+}
+
+// the N-th root (N = 3, 7) of a finite d >= 1, within 1 ulp on every argument tried (the bound the
+// tests hold it to is 4); 1.0 -> 1.0 exactly, inf / NaN -> themselves.  d = m 2^e, e = q N + r with
+// 0 <= r < N, x = m 2^r in [1, 2^N): root(d) = root(x) 2^q.  Start y = ((c2 m + c1) m + c0) 2^(r/N)
+// (a quadratic for m^(1/N) on [1, 2), relative error < 7.2e-4, times a tabulated constant), then
+// three Newton steps y <- y + (x / y^(N-1) - y) (1/N), y^2 = y y, y^6 = (y^2 y)(y^2 y): one
+// division each.  A fixed count: the error goes 7.2e-4 -> 1.6e-6 -> 8e-12 -> rounding for N = 7.
+template <int N>
+MMX_FHD double field_root(double d) {
+  static_assert(N == 3 || N == 7, "root3 and root7 only");
+  if (d == 1.0 || !(d <= kFieldMaxDouble)) return d;
+  int e;
+  const double m = field_split(d, &e);
+  const int q = e / N, r = e - q * N;
+  const double x = m * field_pow2(r);
+  double y;
+  if (N == 3) {
+    const double tab[3] = {1.0, 1.2599210498948732, 1.5874010519681994};
+    y = ((-0.05965740676787307 * m + 0.4374729459679123) * m + 0.6228944233278514) * tab[r];
+  } else {
+    const double tab[7] = {1.0,
+                           1.1040895136738123,
+                           1.2190136542044754,
+                           1.3459001926323562,
+                           1.4859942891369484,
+                           1.640670712015276,
+                           1.8114473285278132};
+    y = ((-0.030509945641418488 * m + 0.19480296734660044) * m + 0.8361453064203973) * tab[r];
+  }
+  constexpr double inv = 1.0 / N;
+#pragma unroll
+  for (int it = 0; it < 3; ++it) {
+    double p = y * y;
+    if (N == 7) {
+      const double y3 = p * y;
+      p = y3 * y3;
+    }
+    y = y + (x / p - y) * inv;
+  }
+  return y * field_pow2(q);
+}
+
+// rho_v = sqrt(det M_v) of the normalised monitor from the Jacobi diagonal l (D values); t (may be
+// null): the divisor of M
+template <int D>
+MMX_FHD double field_huang_rho(const double* l, double alpha, double* t) {
+  double d = (1.0 + l[0] / alpha) * (1.0 + l[1] / alpha);
+  if (D == 3) d = d * (1.0 + l[2] / alpha);
+  if (D == 2) {
+    const double c = field_root<3>(d);
+    if (t) *t = __builtin_sqrt(c);
+    return c;
+  }
+  const double s = field_root<7>(d);
+  if (t) *t = s;
+  return s * s;
+}
+
+// the second recovery of one node (G, D x D, and sw its sum of simplex weights) -> H (may be
+// null), |H|, l and omega
+template <int D>
+MMX_FHD void field_huang_node(const double* G, double sw, double* H, double* A, double* l, double* omega) {
+  double h[D * D];
+  field_symmetrise<D>(G, h);
+  if (H) {
+#pragma unroll
+    for (int i = 0; i < D * D; ++i) H[i] = h[i];
+  }
+  field_abs_sym<D>(h, A, l);
+  *omega = sw / (double)(D + 1);
+}
+
+// M = (I + |H| / alpha) / t
+template <int D>
+MMX_FHD void field_huang_monitor(const double* A, const double* l, double alpha, double* M) {
+  double t;
+  field_huang_rho<D>(l, alpha, &t);
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) M[i] = (((i / D == i % D) ? 1.0 : 0.0) + A[i] / alpha) / t;
+}
+
+// the solve of sigma(alpha) = sum_v omega_v rho_v(alpha) = 2 Omega, a state record advanced once
+// per evaluated sum (on the device by the one-workgroup update kernel, on the host by a loop):
+//   kFieldInit    the pass that sums Omega and takes Lambda = max l is pending
+//   kFieldHalve   trial = hi / 2 is being evaluated (lo == hi: the last trial with sigma <= 2 Omega)
+//   kFieldBisect  trial = lo + (hi - lo) / 2 is being evaluated
+//   kFieldDone    alpha holds the result
+enum FieldPhase { kFieldInit = 0, kFieldHalve = 1, kFieldBisect = 2, kFieldDone = 3 };
+struct FieldSolve {
+  double lo, hi, trial, twoOmega, lambda, alpha;
+  int phase, passes;  // passes: sums evaluated, the Omega pass included
+};
+
+MMX_FHD void field_solve_bisect(FieldSolve* s) {
+  const double mid = s->lo + (s->hi - s->lo) / 2.0;
+  if (mid == s->lo || mid == s->hi) {
+    s->alpha = s->hi;
+    s->phase = kFieldDone;
+  } else {
+    s->trial = mid;
+    s->phase = kFieldBisect;
+  }
+}
+MMX_FHD void field_solve_halve(FieldSolve* s) {
+  const double cand = s->hi * 0.5;
+  if (cand < kFieldMinNormal) {  // would underflow: lo == hi, the bisection ends at once
+    field_solve_bisect(s);
+  } else {
+    s->trial = cand;
+    s->phase = kFieldHalve;
+  }
+}
+// after the first pass: Omega and Lambda.  No root (nothing curved, no volume, or a non-finite
+// input): alpha = 1.0
+MMX_FHD void field_solve_begin(FieldSolve* s, double Omega, double Lambda) {
+  s->passes = 1;
+  s->twoOmega = 2.0 * Omega;
+  s->lambda = Lambda;
+  if (!(Lambda > 0.0 && Lambda <= kFieldMaxDouble && Omega > 0.0 && Omega <= kFieldMaxDouble)) {
+    s->alpha = 1.0;
+    s->phase = kFieldDone;
+    return;
+  }
+  s->lo = Lambda;
+  s->hi = Lambda;
+  field_solve_halve(s);
+}
+// after a pass at s->trial: sigma its sum.  A sum that is not <= 2 Omega (inf and NaN included) is
+// too large
+MMX_FHD void field_solve_advance(FieldSolve* s, double sigma) {
+  s->passes = s->passes + 1;
+  const bool large = !(sigma <= s->twoOmega);
+  if (s->phase == kFieldHalve) {
+    s->lo = s->trial;
+    if (large) {
+      field_solve_bisect(s);
+    } else {
+      s->hi = s->trial;
+      field_solve_halve(s);
+    }
+  } else {
+    if (large)
+      s->lo = s->trial;
+    else
+      s->hi = s->trial;
+    field_solve_bisect(s);
   }
 }
 

@@ -120,6 +120,13 @@ def lib():
     L.mmadmm_get_device.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p]
     L.mmadmm_field_monitor.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_int_p, c_double_p,
                                        ctypes.c_double, c_double_p, c_double_p]
+    L.mmadmm_regrid_field_huang.argtypes = [ctypes.c_void_p, c_double_p, ctypes.c_double, c_double_p]
+    L.mmadmm_regrid_field_huang_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
+                                                   c_double_p]
+    L.mmadmm_field_solve_info.argtypes = [ctypes.c_void_p, c_int_p, c_int_p]
+    L.mmadmm_field_monitor_huang.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_int_p, c_double_p,
+                                             ctypes.c_double, c_double_p, c_double_p, c_double_p]
+    L.mmadmm_field_root.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p]
     L.mmadmm_transfer.argtypes = [ctypes.c_void_p, c_double_p, c_double_p, ctypes.c_int, c_double_p, c_double_p,
                                   c_int_p, c_int_p]
     L.mmadmm_transfer_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
@@ -236,6 +243,26 @@ def field_monitor(Xp, F, u, alpha=None, hessian=True, monitor=True):
                                       float(alpha) if alpha is not None else 1.0,
                                       _dp(H) if H is not None else None, _dp(M) if M is not None else None))
     return H, M
+
+
+def field_monitor_huang(Xp, F, u, alpha=None):
+    """mmadmm_field_monitor_huang (host only, no device): the recovered Hessian H and Huang's normalised
+    monitor M = det(I + |H| / alpha)^(-1/(D+4)) (I + |H| / alpha), each nP x D x D -> (H, M, alpha_used).
+    alpha None: solved from the equidistribution equation sum omega rho(alpha) = 2 sum omega (1.0 when
+    H = 0 everywhere).  Bit-identical to Engine.regrid_field(u, alpha, normalise=True) with
+    F = Engine.simplices()."""
+    Xp = np.ascontiguousarray(Xp, dtype=np.float64)
+    F = np.ascontiguousarray(F, dtype=np.int32)
+    u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+    nP, D = Xp.shape
+    if u.shape[0] != nP or F.ndim != 2 or F.shape[1] != D + 1:
+        raise ValueError("field_monitor_huang: Xp nP x D, F nF x (D + 1), u nP values")
+    H, M = np.zeros((nP, D, D)), np.zeros((nP, D, D))
+    used = ctypes.c_double(0.0)
+    _check(lib().mmadmm_field_monitor_huang(D, nP, _dp(Xp), F.shape[0], _ip(F), _dp(u),
+                                            0.0 if alpha is None else float(alpha), ctypes.byref(used), _dp(H),
+                                            _dp(M)))
+    return H, M, used.value
 
 
 TRANSFER_COUNTS = ("copied", "patch", "walked", "outside")
@@ -804,10 +831,26 @@ class Engine:
         _check(lib().mmadmm_field_hessian(self.h, _dp(u), _dp(H)))
         return H
 
-    def regrid_field(self, u, alpha=None):
+    def regrid_field(self, u, alpha=None, normalise=False):
         """Rebuild the monitor grid from the nodal scalar field u: M = I + |H| / alpha, H the recovered
         Hessian.  alpha None: the mean Frobenius norm of field_hessian(u) (1.0 when that is 0).
+        normalise=True: Huang's metric M = det(I + |H| / alpha)^(-1/(D+4)) (I + |H| / alpha), and
+        alpha None is solved on the device from the equidistribution equation (include/mmadmm.h:
+        mmadmm_regrid_field_huang); pass the returned alpha to later calls to skip the solve.
         Returns the alpha used."""
+        if normalise:
+            used = ctypes.c_double(0.0)
+            alpha = 0.0 if alpha is None else float(alpha)
+            if _is_tensor(u):
+                p, st, j = self._device_arg(u, self.nP, "regrid_field")
+                _check(lib().mmadmm_regrid_field_huang_device(self.h, p, alpha, st, ctypes.byref(used)))
+                self._rejoin(j)
+                return used.value
+            u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+            if u.size != self.nP:
+                raise ValueError(f"regrid_field: u must hold {self.nP} values")
+            _check(lib().mmadmm_regrid_field_huang(self.h, _dp(u), alpha, ctypes.byref(used)))
+            return used.value
         if alpha is None:
             H = self.field_hessian(u)
             if _is_tensor(H):
@@ -827,6 +870,13 @@ class Engine:
             raise ValueError(f"regrid_field: u must hold {self.nP} values")
         _check(lib().mmadmm_regrid_field(self.h, _dp(u), alpha))
         return alpha
+
+    def field_solve_info(self):
+        """(sums evaluated, state read-backs) of the last regrid_field(..., normalise=True) that solved
+        alpha; (0, 0) after a given alpha."""
+        passes, syncs = ctypes.c_int(0), ctypes.c_int(0)
+        _check(lib().mmadmm_field_solve_info(self.h, ctypes.byref(passes), ctypes.byref(syncs)))
+        return passes.value, syncs.value
 
     def transfer(self, u, X_old, X_new=None, where=False):
         """The nodal field u (nP or nP x C values at the old node positions X_old, nP x D) evaluated at the
