@@ -215,6 +215,49 @@ int mmadmm_transfer_field(int dim, int nP, const double* Xold, int nF, const int
  * the face of s opposite its local vertex j, or -1. */
 int mmadmm_face_neighbours(int dim, int nP, int nF, const int32_t* F, int32_t* nbr);
 
+/* ---- mesh quality against a monitor (no reference counterpart)
+ * Huang's three element-wise measures of the engine's mesh, computed on the device.  For simplex K
+ * of mmadmm_get_simplices at the positions X (nP x D; NULL: the engine's current "points"): E its
+ * edge matrix (columns X[v_{j+1}] - X[v0]), Ehat the engine's reference simplex ("Ehat"; with a
+ * computational mesh the edge matrix of K in Xc), J = E Ehat^-1, M_K the mean of the vertices'
+ * monitor tensors, A = J^T M_K J, det A = (det E / det Ehat)^2 det M_K.
+ *   Q_geo  ((tr J^T J / D)^D / det J^T J)^(1/(2(D-1))): the shape of K against its reference
+ *          simplex; >= 1, = 1 iff similar to it
+ *   Q_ali  the same with A: >= 1, = 1 iff K is aligned with M_K; with M = I it is Q_geo
+ *   Q_eq   (e_K / sigma) / (c_K / Vhat), e_K = vol_K sqrt(det M_K), c_K = |det Ehat| / D!,
+ *          sigma = sum e_K, Vhat = sum c_K: its maximum is 1 iff the mesh is equidistributed
+ * Only + - * / sqrt, the sums in a fixed tree order over blocks of 256 simplex ids: bitwise
+ * reproducible, the same bits from mmadmm_mesh_quality on the host and tests/quality_py.py.
+ * source: MMADMM_QUALITY_IDENTITY (M = I: Q_ali = Q_geo, Q_eq measures pure volume; M ignored),
+ * MMADMM_QUALITY_VALUES (M: the caller's nodal tensors, nP x D*D row-major), MMADMM_QUALITY_LAST (the
+ * nodal monitor of the engine's last grid rebuild, whichever mmadmm_regrid* call or time-varying
+ * step made it; M ignored).  The tensors of LAST stay attached to node ids: after a step they are
+ * the monitor at the pre-step positions.
+ * q (3 x nF component-major: rows Q_geo, Q_ali, Q_eq) and summary (8 host doubles) may each be NULL,
+ * not both.  summary: {max Q_geo, max Q_ali, max Q_eq, mean Q_geo, mean Q_ali, sigma, |Omega| = sum
+ * vol_K, number of invalid simplices}.  A simplex is invalid when det E is not > 0, det Ehat is 0 or
+ * NaN, or det M_K is not > 0 (a NaN fails each test): its three measures are +inf, it adds nothing to
+ * sigma and |Omega|, its c_K (unless not finite) to Vhat, and it is counted; nothing is divided or
+ * rooted before the test, so inverted input is ordinary arithmetic, not an error.  The two means are
+ * +inf as soon as one simplex is invalid.
+ * The _device form reads and writes device arrays ordered after `stream`'s work and hands q back to
+ * it with no host synchronisation; asking for summary costs one small read-back and a host wait.
+ * stream NULL: the data are ready, and the call returns when the results are.  Refused
+ * (MMADMM_ERR_INVALID): an element partition (single rank only), q and summary both NULL, an unknown
+ * source, VALUES without M, LAST before any rebuild. */
+#define MMADMM_QUALITY_IDENTITY 0
+#define MMADMM_QUALITY_VALUES 1
+#define MMADMM_QUALITY_LAST 2
+int mmadmm_quality(mmadmm_handle h, const double* X, int source, const double* M, double* q, double* summary);
+int mmadmm_quality_device(mmadmm_handle h, const double* d_X, int source, const double* d_M, double* d_q,
+                          double* summary, void* stream);
+/* Host only, no device needed: the same measures on the CPU in the kernels' arithmetic (bit-identical
+ * to the calls above with F = mmadmm_get_simplices' simplices: F is used as given, not re-oriented).
+ * Xc (nP x dim) NULL: Ehat (dim x dim row-major, as mmadmm_get "Ehat") is required and serves every
+ * simplex.  M NULL: the identity. */
+int mmadmm_mesh_quality(int dim, int nP, const double* Xp, const double* Xc, int nF, const int32_t* F,
+                        const double* Ehat, const double* M, double* q, double* summary);
+
 const char* mmadmm_last_error(void);
 int mmadmm_version(void);
 /* provenance (no reference counterpart): "src_hash=<16 hex> git=<describe> arch=gfx950", the hash of

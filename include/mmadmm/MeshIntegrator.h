@@ -112,6 +112,17 @@ public:
         mmadmm_cxx::check(onDevice ? mmadmm_transfer_device(h_, Xold, nullptr, C, uold, unew, nullptr, nullptr, nullptr)
                                    : mmadmm_transfer(h_, Xold, nullptr, C, uold, unew, nullptr, nullptr));
     }
+    // Huang's geometry, alignment and equidistribution measures of the current mesh (X null) or of the
+    // candidate positions X (nP x D row-major) against the monitor `source`: MMADMM_QUALITY_IDENTITY,
+    // _VALUES (M: nP x D*D nodal tensors) or _LAST (the nodal monitor of the last grid rebuild, e.g. of
+    // regridFromFieldHuang).  q (3 x nF component-major: Q_geo, Q_ali, Q_eq) and summary (8 host
+    // doubles) may each be null, not both (no reference counterpart; include/mmadmm.h: mmadmm_quality
+    // and mmadmm_quality_device).  onDevice: X, M and q are in device memory and ready
+    void quality(int source, const double *M, double *q, double *summary, const double *X = nullptr,
+                 bool onDevice = false) {
+        mmadmm_cxx::check(onDevice ? mmadmm_quality_device(h_, X, source, M, q, summary, nullptr)
+                                   : mmadmm_quality(h_, X, source, M, q, summary));
+    }
     // the engine behind this integrator, for the C-ABI calls the reference's class has no name for
     mmadmm_handle handle() const { return h_; }
 

@@ -16,6 +16,7 @@
 #include "../../../include/mmx_sparse.h"
 #include "../kernels/admm_kernels.h"
 #include "../kernels/field_kernels.h"
+#include "../kernels/quality_kernels.h"
 #include "../kernels/regrid_kernels.h"
 #include "../kernels/transfer_kernels.h"
 #include "comm.h"
@@ -70,6 +71,9 @@ struct EngineBase {
   // mmadmm_transfer(_device): nodal fields from the old node positions to the new ones (Xnew null: Vp)
   virtual void transfer(const double* Xold, const double* Xnew, int C, const double* uold, double* unew, int32_t* where,
                         int* counts, bool onDevice, void* stream) = 0;
+  // mmadmm_quality(_device): Huang's measures of the mesh at X (null: Vp) against the monitor `source`
+  virtual void quality(const double* X, int source, const double* M, double* q, double* summary, bool onDevice,
+                       void* stream) = 0;
   virtual void debugBlockGrad(int s, const double* z, const double* dx, int flags, double* out) = 0;
   virtual std::string options() const = 0;
 };
@@ -331,6 +335,7 @@ class Engine final : public EngineBase {
   ~Engine() override {
     if (rgHost_) (void)hipHostFree(rgHost_);
     if (fldStH_) (void)hipHostFree(fldStH_);
+    if (qlRecH_) (void)hipHostFree(qlRecH_);
     if (rgnHost_) (void)hipHostFree(rgnHost_);
     if (jac_) (void)mmx_matrix_destroy(jac_);
     for (auto& e : evPool_) (void)hipEventDestroy(e);
@@ -1201,6 +1206,70 @@ class Engine final : public EngineBase {
     if (counts) transfer_sum_counts(cnt, counts);
   }
 
+  // e_K (when the caller wants no q), c_K (computational mesh), the partials, the record and its
+  // pinned host copy: allocated at an engine's first quality call
+  void qualityScratch() {
+    if (qlPart_.p) return;
+    qlE_.alloc(std::max(nF_, 1));
+    if (compMesh_) qlC_.alloc(std::max(nF_, 1));
+    qlPart_.alloc(std::max<size_t>(quality_part_doubles(nF_), 1));
+    qlRec_.alloc(kQualityRecord);
+    MMX_HIP(hipHostMalloc((void**)&qlRecH_, sizeof(double) * kQualityRecord, hipHostMallocDefault));
+  }
+
+  // mmadmm_quality / mmadmm_quality_device (quality_kernels.hip)
+  void quality(const double* X, int source, const double* M, double* q, double* summary, bool onDevice,
+               void* stream) override {
+    const std::string who = onDevice ? "mmadmm_quality_device" : "mmadmm_quality";
+    singleRankOnly(who.c_str());
+    if (source != kQualityIdentity && source != kQualityValues && source != kQualityLast)
+      throw Error(MMADMM_ERR_INVALID, who + ": unknown monitor source");
+    if (source == kQualityValues && !M) throw Error(MMADMM_ERR_INVALID, who + ": MMADMM_QUALITY_VALUES needs M");
+    if (source == kQualityLast && !rgMon_.p)
+      throw Error(MMADMM_ERR_INVALID, who + ": MMADMM_QUALITY_LAST before any rebuild of the monitor grid");
+    if (!q && !summary) throw Error(MMADMM_ERR_INVALID, who + ": q and summary are both NULL");
+    qualityScratch();
+    QualityRef ref;
+    for (int i = 0; i < 9; ++i) ref.Ehat[i] = i < D * D ? EhatH_[i] : 0.0;
+    const double* Xc = compMesh_ ? Vc_.p : nullptr;
+    const size_t nx = (size_t)nP_ * D, nm = (size_t)nP_ * D * D, nq = (size_t)3 * nF_;
+    if (!onDevice) {  // staged through the same kernels; the host arrays are done with when the call returns
+      const size_t need = (X ? nx : 0) + (source == kQualityValues ? nm : 0) + (q ? nq : 0);
+      if (qlStage_.n < need) qlStage_.alloc(need);
+      double* at = qlStage_.p;
+      const double *dX = Vp_.p, *dM = source == kQualityLast ? rgMon_.p : nullptr;
+      double* dq = nullptr;
+      if (X) {
+        MMX_HIP(hipMemcpyAsync(at, X, nx * sizeof(double), hipMemcpyHostToDevice, st_));
+        dX = at;
+        at += nx;
+      }
+      if (source == kQualityValues) {
+        MMX_HIP(hipMemcpyAsync(at, M, nm * sizeof(double), hipMemcpyHostToDevice, st_));
+        dM = at;
+        at += nm;
+      }
+      if (q) dq = at;
+      launch_quality<D>(dX, F_.p, nF_, dM, Xc, ref, dq, qlE_.p, qlC_.p, qlPart_.p, qlRec_.p, st_);
+      MMX_HIP(hipGetLastError());
+      if (q) MMX_HIP(hipMemcpyAsync(q, dq, nq * sizeof(double), hipMemcpyDeviceToHost, st_));
+      if (summary)
+        MMX_HIP(hipMemcpyAsync(qlRecH_, qlRec_.p, sizeof(double) * kQualityRecord, hipMemcpyDeviceToHost, st_));
+      streamWait();
+    } else {
+      afterProducer(stream);
+      launch_quality<D>(X ? X : Vp_.p, F_.p, nF_,
+                        source == kQualityValues ? M : source == kQualityLast ? rgMon_.p : nullptr, Xc, ref, q, qlE_.p,
+                        qlC_.p, qlPart_.p, qlRec_.p, st_);
+      MMX_HIP(hipGetLastError());
+      if (summary)
+        MMX_HIP(hipMemcpyAsync(qlRecH_, qlRec_.p, sizeof(double) * kQualityRecord, hipMemcpyDeviceToHost, st_));
+      beforeConsumer(stream);
+      if (summary && stream) streamWait();  // the read-back; without a summary the host does not wait
+    }
+    if (summary) std::memcpy(summary, qlRecH_, 8 * sizeof(double));
+  }
+
   // mmadmm_get_device: "x" or "points" into the caller's device array
   void getDevice(const std::string& what, double* dOut, void* stream) override {
     singleRankOnly("mmadmm_get_device");
@@ -1831,6 +1900,8 @@ class Engine final : public EngineBase {
   std::vector<int32_t> trNbrH_;  // the transfer's face-neighbour table (host copy) and device scratch
   DevBuf<int32_t> trNbr_, trWhere_, trCnt_;
   DevBuf<double> trStage_;
+  DevBuf<double> qlE_, qlC_, qlPart_, qlRec_, qlStage_;  // the quality measures' scratch (qualityScratch)
+  double* qlRecH_ = nullptr;
   const double* srcPtr_ = nullptr;
   double srcAlpha_ = 1.0;
   hipEvent_t evIn_ = nullptr, evOut_ = nullptr;
@@ -2182,6 +2253,13 @@ int mmadmm_transfer_device(mmadmm_handle h, const double* d_Xold, const double* 
     check_transfer("mmadmm_transfer_device", d_Xold, C, d_uold, d_unew);
     eng(h).transfer(d_Xold, d_Xnew, C, d_uold, d_unew, d_where, counts, true, stream);
   });
+}
+int mmadmm_quality(mmadmm_handle h, const double* X, int source, const double* M, double* q, double* summary) {
+  return guarded([&] { eng(h).quality(X, source, M, q, summary, false, nullptr); });
+}
+int mmadmm_quality_device(mmadmm_handle h, const double* d_X, int source, const double* d_M, double* d_q,
+                          double* summary, void* stream) {
+  return guarded([&] { eng(h).quality(d_X, source, d_M, d_q, summary, true, stream); });
 }
 int mmadmm_get_device(mmadmm_handle h, const char* what, double* d_out, void* consumer_stream) {
   return guarded([&] {

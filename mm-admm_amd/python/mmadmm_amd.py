@@ -134,6 +134,11 @@ def lib():
     L.mmadmm_transfer_field.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_int_p, c_double_p,
                                         ctypes.c_int, c_double_p, c_double_p, c_int_p, c_int_p]
     L.mmadmm_face_neighbours.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, c_int_p]
+    L.mmadmm_quality.argtypes = [ctypes.c_void_p, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_double_p]
+    L.mmadmm_quality_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                        ctypes.c_void_p, c_double_p, ctypes.c_void_p]
+    L.mmadmm_mesh_quality.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_int_p,
+                                      c_double_p, c_double_p, c_double_p, c_double_p]
     L.mmadmm_destroy.argtypes = [ctypes.c_void_p]
     L.mmadmm_mesh_rect.argtypes = [ctypes.c_int] * 4 + [ctypes.c_double] * 6 + [ctypes.c_int,
                                                                                  ctypes.POINTER(ctypes.c_void_p)]
@@ -309,6 +314,49 @@ def face_neighbours(F, nP=None):
     _check(lib().mmadmm_face_neighbours(F.shape[1] - 1, int(F.max()) + 1 if nP is None else nP, F.shape[0], _ip(F),
                                         _ip(nbr)))
     return nbr
+
+
+QUALITY_IDENTITY, QUALITY_VALUES, QUALITY_LAST = 0, 1, 2  # MMADMM_QUALITY_*
+QUALITY_SUMMARY = ("max_geo", "max_ali", "max_eq", "mean_geo", "mean_ali", "sigma", "volume", "invalid")
+
+
+def _quality_summary(s):
+    out = {k: float(v) for k, v in zip(QUALITY_SUMMARY, s)}
+    out["invalid"] = int(s[7])
+    return out
+
+
+def mesh_quality(Xp, F, M=None, Xc=None, Ehat=None):
+    """mmadmm_mesh_quality (host only, no device): Huang's geometry, alignment and equidistribution
+    measures of the mesh (Xp, F) against the nodal monitor tensors M (nP x D x D; None: the identity)
+    -> (q, summary): q is 3 x nF (rows Q_geo, Q_ali, Q_eq), summary a dict of QUALITY_SUMMARY.  The
+    reference simplex of every element is its own in the computational mesh Xc, or, without one, the
+    constant Ehat (D x D, Engine.get("Ehat")).  An invalid simplex (not positively oriented, a reference
+    simplex of no volume, det M_K not > 0) has +inf in all three rows and is counted in "invalid".  F
+    is used as given: pass Engine.simplices() to reproduce Engine.quality bit for bit."""
+    Xp = np.ascontiguousarray(Xp, dtype=np.float64)
+    F = np.ascontiguousarray(F, dtype=np.int32)
+    if Xp.ndim != 2 or F.ndim != 2 or F.shape[1] != Xp.shape[1] + 1:
+        raise ValueError("mesh_quality: Xp nP x D, F nF x (D + 1)")
+    nP, D = Xp.shape
+    if Xc is not None:
+        Xc = np.ascontiguousarray(Xc, dtype=np.float64)
+        if Xc.shape != Xp.shape:
+            raise ValueError("mesh_quality: Xc must have the shape of Xp")
+    if Ehat is not None:
+        Ehat = np.ascontiguousarray(Ehat, dtype=np.float64)
+        if Ehat.size != D * D:
+            raise ValueError("mesh_quality: Ehat must hold D x D values")
+    if M is not None:
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        if M.size != nP * D * D:
+            raise ValueError("mesh_quality: M must hold nP x D x D values")
+    q = np.zeros((3, F.shape[0]))
+    s = np.zeros(8)
+    _check(lib().mmadmm_mesh_quality(D, nP, _dp(Xp), _dp(Xc) if Xc is not None else None, F.shape[0], _ip(F),
+                                     _dp(Ehat) if Ehat is not None else None, _dp(M) if M is not None else None,
+                                     _dp(q), _dp(s)))
+    return q, _quality_summary(s)
 
 
 def _is_tensor(a):
@@ -928,6 +976,55 @@ class Engine:
         if where:
             info["where"] = w
         return out, info
+
+    def quality(self, M=None, X=None, per_simplex=True):
+        """Huang's geometry, alignment and equidistribution measures of the mesh (include/mmadmm.h:
+        mmadmm_quality) -> (q, summary): q is 3 x nF (rows Q_geo, Q_ali, Q_eq; None when per_simplex is
+        False), summary a dict of QUALITY_SUMMARY (reading it waits for the kernels).  M: None for the
+        identity, "last" for the nodal monitor of the engine's last grid rebuild (attached to node ids:
+        after a step, the monitor at the pre-step positions), or nodal tensors nP x D x D.  X: candidate
+        node positions (nP x D), None for the engine's current "points".  Numpy arrays go through the
+        host call, float64 CUDA tensors through the _device call on torch's current stream; q is of
+        the kind given (an array when neither M nor X is a tensor)."""
+        if isinstance(M, str):
+            if M != "last":
+                raise ValueError("quality: M is None, 'last', an array or a tensor")
+            source, M = QUALITY_LAST, None
+        else:
+            source = QUALITY_IDENTITY if M is None else QUALITY_VALUES
+        nx, nm = self.nP * self.dim, self.nP * self.dim * self.dim
+        s = np.zeros(8)
+        if _is_tensor(M) or _is_tensor(X):
+            import torch
+
+            if not all(a is None or _is_tensor(a) for a in (M, X)):
+                raise ValueError("quality: M and X must both be tensors or both be arrays")
+            pm = px = st = j = None
+            if M is not None:
+                pm, st, j = self._device_arg(M, nm, "quality")
+            if X is not None:
+                px, st, j = self._device_arg(X, nx, "quality")
+            q = None
+            if per_simplex:
+                q = torch.empty((3, self.nF), dtype=torch.float64, device=(M if M is not None else X).device)
+                if j is not None:
+                    q.record_stream(j[1])
+            _check(lib().mmadmm_quality_device(self.h, px, source, pm, q.data_ptr() if per_simplex else None, _dp(s),
+                                               st))
+            self._rejoin(j)
+            return q, _quality_summary(s)
+        if M is not None:
+            M = np.ascontiguousarray(M, dtype=np.float64)
+            if M.size != nm:
+                raise ValueError(f"quality: M must hold {nm} values")
+        if X is not None:
+            X = np.ascontiguousarray(X, dtype=np.float64)
+            if X.size != nx:
+                raise ValueError(f"quality: X must hold {nx} values")
+        q = np.zeros((3, self.nF)) if per_simplex else None
+        _check(lib().mmadmm_quality(self.h, _dp(X) if X is not None else None, source,
+                                    _dp(M) if M is not None else None, _dp(q) if per_simplex else None, _dp(s)))
+        return q, _quality_summary(s)
 
     def get_tensor(self, what):
         """get("points" | "x") as a float64 CUDA tensor (nP x D), copied on the device and ordered
