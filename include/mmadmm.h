@@ -186,6 +186,45 @@ int mmadmm_field_monitor_huang(int dim, int nP, const double* Xp, int nF, const 
                                double alpha, double* alpha_used, double* H, double* M);
 int mmadmm_field_root(int n, int count, const double* d, double* out);
 
+/* The monitor from several solution components: U holds C components per node (nP x C
+ * row-major, the layout of mmadmm_transfer's uold), 1 <= C <= 32, and the metric is Huang & Russell's
+ * sum of absolute Hessians
+ *   A_v = w_0 |H_0|_v + w_1 |H_1|_v + ... + w_{C-1} |H_{C-1}|_v     (ascending c, from the first product),
+ * H_c the recovered Hessian of column c, bit-identical to mmadmm_field_hessian of that column.  w: C
+ * weights, each finite and > 0, a HOST array in every form (the _device forms included), read before
+ * the call returns; NULL means all 1.0.
+ *   mmadmm_regrid_fields:        M_v = I + A_v / alpha, alpha finite and > 0.  With C = 1 and w NULL
+ *                                bit-identical to mmadmm_regrid_field.
+ *   mmadmm_regrid_fields_huang:  M_v = (I + A_v / alpha) / t_v, Huang's normalisation with l the Jacobi
+ *                                diagonal of A_v; alpha given, or 0.0: solved on the device by the search of
+ *                                mmadmm_regrid_field_huang (alpha_used, mmadmm_field_solve_info as there).
+ *                                With C = 1 it agrees with mmadmm_regrid_field_huang to rounding, not bit
+ *                                for bit (l comes from a second Jacobi, on |H| instead of H); the last
+ *                                bits depend on the order of the components.
+ *   mmadmm_field_hessians:       H (nP x C x D*D) and / or A (nP x D*D); not both NULL.
+ * 2 ceil(C / D) + 2 C kernel launches for the recovery, against 4 C for C scalar calls.  Stream
+ * hand-over, staging of host arrays, the rebuild and the single-rank refusal are those of
+ * mmadmm_regrid_field(_device) / mmadmm_field_hessian(_device).  MMADMM_ERR_INVALID: C out of range, a
+ * NULL U, a weight that is zero, negative or not finite, a bad alpha.  A NaN in a component reaches the
+ * nodes its recovery reaches; the solve still ends (a fixed number of steps at most).
+ * mmadmm_fields_monitor is the host-only twin (no device), bit-identical to the calls above with
+ * F = mmadmm_get_simplices' simplices (F is used as given): H, A, M and alpha_used may each be NULL;
+ * alpha is checked only when M is asked for (normalise == 0: finite and > 0; else 0.0 means solved);
+ * alpha_used receives the alpha the monitor was (or would be) built with. */
+int mmadmm_regrid_fields(mmadmm_handle h, int C, const double* U, const double* w, double alpha);
+int mmadmm_regrid_fields_device(mmadmm_handle h, int C, const double* d_U, const double* w, double alpha,
+                                void* producer_stream);
+int mmadmm_regrid_fields_huang(mmadmm_handle h, int C, const double* U, const double* w, double alpha,
+                               double* alpha_used);
+int mmadmm_regrid_fields_huang_device(mmadmm_handle h, int C, const double* d_U, const double* w, double alpha,
+                                      void* producer_stream, double* alpha_used);
+int mmadmm_field_hessians(mmadmm_handle h, int C, const double* U, const double* w, double* H, double* A);
+int mmadmm_field_hessians_device(mmadmm_handle h, int C, const double* d_U, const double* w, double* d_H, double* d_A,
+                                 void* stream);
+int mmadmm_fields_monitor(int dim, int nP, const double* Xp, int nF, const int32_t* F, int C, const double* U,
+                          const double* w, double alpha, int normalise, double* alpha_used, double* H, double* A,
+                          double* M);
+
 /* ---- nodal fields onto the moved mesh (no reference counterpart)
  * After mmadmm_step the nodes have moved and u[v] still holds the caller's field at the old position
  * of node v.  mmadmm_transfer evaluates the piecewise-linear field (old positions Xold, nP x D;

@@ -104,6 +104,21 @@ public:
                                    : mmadmm_regrid_field_huang(h_, u, alpha, &used));
         return used;
     }
+    // the same two monitors from C components per node (U nP x C row-major, as transferField carries
+    // them): the metric is the weighted sum of the components' absolute Hessians, w C host weights
+    // (nullptr: all 1) whatever onDevice says (include/mmadmm.h: mmadmm_regrid_fields(_huang) and
+    // their _device forms)
+    void regridFromFields(const double *U, int C, const double *w, double alpha, bool onDevice = false) {
+        mmadmm_cxx::check(onDevice ? mmadmm_regrid_fields_device(h_, C, U, w, alpha, nullptr)
+                                   : mmadmm_regrid_fields(h_, C, U, w, alpha));
+    }
+    double regridFromFieldsHuang(const double *U, int C, const double *w = nullptr, double alpha = 0.0,
+                                 bool onDevice = false) {
+        double used = 0.0;
+        mmadmm_cxx::check(onDevice ? mmadmm_regrid_fields_huang_device(h_, C, U, w, alpha, nullptr, &used)
+                                   : mmadmm_regrid_fields_huang(h_, C, U, w, alpha, &used));
+        return used;
+    }
     // the caller's nodal field (C components per node, nP x C row-major) carried from the node
     // positions Xold (nP x D row-major, e.g. those before step()) to the current ones, piecewise
     // linearly on the old mesh (no reference counterpart; include/mmadmm.h: mmadmm_transfer and

@@ -64,6 +64,12 @@ struct EngineBase {
   // mmadmm_get_device): src = kMonValues (nP x D*D tensors) or kMonField (nP values of a scalar field)
   virtual void regridFrom(int src, const double* p, bool onDevice, double alpha, void* stream) = 0;
   virtual void fieldHessian(const double* u, double* H, bool onDevice, void* stream) = 0;
+  // mmadmm_regrid_fields(_huang)(_device) / mmadmm_field_hessians(_device): the metric of C components
+  // (U nP x C, w C checked host weights); src = kMonFields or kMonFieldsHuang
+  virtual void regridFromFields(int src, const double* U, int C, const double* w, bool onDevice, double alpha,
+                                void* stream) = 0;
+  virtual void fieldHessians(const double* U, int C, const double* w, double* H, double* A, bool onDevice,
+                             void* stream) = 0;
   // the alpha of the last regridFrom(kMonFieldHuang, ...): the given one, or the one solved
   virtual double fieldAlphaUsed() const = 0;
   virtual void fieldSolveInfo(int* passes, int* syncs) const = 0;
@@ -81,7 +87,15 @@ struct EngineBase {
 // Mesh::reOrientElements (src/Mesh.cpp:243-260): swap F(i,1), F(i,2) when det(E) < 0, E the
 // edge vectors from vertex 0 as columns, Eigen's 2x2 / 3x3 determinant
 // the source of the monitor at the vertices of a grid rebuild (regridAll)
-enum MonSource { kMonBuiltin7 = 0, kMonCallback = 1, kMonValues = 2, kMonField = 3, kMonFieldHuang = 4 };
+enum MonSource {
+  kMonBuiltin7 = 0,
+  kMonCallback = 1,
+  kMonValues = 2,
+  kMonField = 3,
+  kMonFieldHuang = 4,
+  kMonFields = 5,
+  kMonFieldsHuang = 6
+};
 
 void reorient_simplices(int D, const double* Vp, int nF, int32_t* F) {
   for (int s = 0; s < nF; ++s) {
@@ -1075,6 +1089,11 @@ class Engine final : public EngineBase {
     fldE_.alloc(std::max<size_t>(field_ebuf_doubles<D>(nF_), 1));
     fldG_.alloc((size_t)nP_ * D);
   }
+  // C components: one gradient plane (nP x D) each, allocated at the first call, grown by a larger C
+  void fieldsScratch(int C) {
+    fieldScratch();
+    if (fldGP_.n < (size_t)C * nP_ * D) fldGP_.alloc((size_t)C * nP_ * D);
+  }
   // Huang's monitor: |H|, {l, omega}, the partial sums of a pass, the search's state record and its
   // pinned host copy
   void huangScratch() {
@@ -1093,6 +1112,17 @@ class Engine final : public EngineBase {
     huangScratch();
     launch_field_huang_recover<D>(X, srcPtr_, F_.p, nF_, incPtr_.p, incOff_.p, nodeOrder_.p, nP_, fldE_.p, fldG_.p,
                                   fldA_.p, fldL_.p, st_);
+    huangSolveAndFinish();
+  }
+  // the same of the C components srcPtr_ (nP x srcC_, weights srcW_): only the producer of fldA_ / fldL_ differs
+  void fieldsHuangMonitor(const double* X) {
+    fieldsScratch(srcC_);
+    huangScratch();
+    launch_fields_recover<D>(X, srcPtr_, srcC_, srcW_.data(), F_.p, nF_, incPtr_.p, incOff_.p, nodeOrder_.p, nP_,
+                             fldE_.p, fldGP_.p, nullptr, fldA_.p, kFieldsHuang, 1.0, fldL_.p, st_);
+    huangSolveAndFinish();
+  }
+  void huangSolveAndFinish() {
     launch_field_solve_set(fldSt_.p, srcAlpha_, st_);
     fldAlphaUsed_ = srcAlpha_;
     fldPasses_ = fldSyncs_ = 0;
@@ -1136,6 +1166,55 @@ class Engine final : public EngineBase {
     srcPtr_ = nullptr;
     // the caller's array has been read: by the host wait of updateIso, else here (MMX_ISO=0)
     if (onDevice && !knobs_.iso) streamWait();
+  }
+
+  // mmadmm_regrid_fields(_huang)(_device): regridFrom of C components, U staged or ordered in the same way
+  void regridFromFields(int src, const double* U, int C, const double* w, bool onDevice, double alpha,
+                        void* stream) override {
+    singleRankOnly(src == kMonFieldsHuang ? "mmadmm_regrid_fields_huang" : "mmadmm_regrid_fields");
+    const size_t n = (size_t)nP_ * C;
+    if (!onDevice) {
+      if (fldIn_.n < n) fldIn_.alloc(n);
+      MMX_HIP(hipMemcpyAsync(fldIn_.p, U, n * sizeof(double), hipMemcpyHostToDevice, st_));
+      streamWait();
+      U = fldIn_.p;
+    } else {
+      afterProducer(stream);
+    }
+    srcPtr_ = U;
+    srcAlpha_ = alpha;
+    srcC_ = C;
+    srcW_.assign(w, w + C);
+    regridAll(0.0, (MonSource)src);
+    srcPtr_ = nullptr;
+    if (onDevice && !knobs_.iso) streamWait();
+  }
+
+  // mmadmm_field_hessians: every component's Hessian (nP x C x D*D) and / or the metric A (nP x D*D)
+  void fieldHessians(const double* U, int C, const double* w, double* H, double* A, bool onDevice,
+                     void* stream) override {
+    singleRankOnly("mmadmm_field_hessians");
+    fieldsScratch(C);
+    const size_t nU = (size_t)nP_ * C, nH = H ? nU * D * D : 0, nA = A ? (size_t)nP_ * D * D : 0;
+    if (!onDevice) {
+      if (fldIn_.n < nU) fldIn_.alloc(nU);
+      if (fldOut_.n < nH + nA) fldOut_.alloc(nH + nA);
+      MMX_HIP(hipMemcpyAsync(fldIn_.p, U, nU * sizeof(double), hipMemcpyHostToDevice, st_));
+      double* dH = H ? fldOut_.p : nullptr;
+      double* dA = A ? fldOut_.p + nH : nullptr;
+      launch_fields_recover<D>(Vp_.p, fldIn_.p, C, w, F_.p, nF_, incPtr_.p, incOff_.p, nodeOrder_.p, nP_, fldE_.p,
+                               fldGP_.p, dH, dA, kFieldsNone, 1.0, nullptr, st_);
+      MMX_HIP(hipGetLastError());
+      if (H) MMX_HIP(hipMemcpyAsync(H, dH, nH * sizeof(double), hipMemcpyDeviceToHost, st_));
+      if (A) MMX_HIP(hipMemcpyAsync(A, dA, nA * sizeof(double), hipMemcpyDeviceToHost, st_));
+      streamWait();
+      return;
+    }
+    afterProducer(stream);
+    launch_fields_recover<D>(Vp_.p, U, C, w, F_.p, nF_, incPtr_.p, incOff_.p, nodeOrder_.p, nP_, fldE_.p, fldGP_.p, H,
+                             A, kFieldsNone, 1.0, nullptr, st_);
+    MMX_HIP(hipGetLastError());
+    beforeConsumer(stream);
   }
 
   // mmadmm_field_hessian: the recovered Hessian alone (nP x D*D)
@@ -1669,6 +1748,12 @@ class Engine final : public EngineBase {
                               srcAlpha_, nullptr, rgMon_.p, st_);
     } else if (src == kMonFieldHuang) {
       fieldHuangMonitor(X);
+    } else if (src == kMonFields) {  // the metric accumulates in rgMon_, the last launch leaves M there
+      fieldsScratch(srcC_);
+      launch_fields_recover<D>(X, srcPtr_, srcC_, srcW_.data(), F_.p, nF_, incPtr_.p, incOff_.p, nodeOrder_.p, nP_,
+                               fldE_.p, fldGP_.p, nullptr, rgMon_.p, kFieldsPlain, srcAlpha_, nullptr, st_);
+    } else if (src == kMonFieldsHuang) {
+      fieldsHuangMonitor(X);
     } else if (src == kMonBuiltin7) {
       double c[3];
       moving_bump_centre(t, c);
@@ -1889,6 +1974,9 @@ class Engine final : public EngineBase {
   // the monitor from the caller's arrays (regridFrom): the element buffer and nodal gradient of the
   // recovery, staged host input / output, the source of the rebuild in flight, the caller-stream events
   DevBuf<double> fldE_, fldG_, fldIn_, fldOut_;
+  DevBuf<double> fldGP_;       // several components (regridFromFields): their gradient planes, C x nP x D,
+  int srcC_ = 1;               // and of the rebuild in flight the component count and the weights
+  std::vector<double> srcW_;
   // Huang's monitor (fieldHuangMonitor): |H|, {l, omega}, a pass's partials, the search's state record
   // (device, pinned host copy), and of the last call the alpha used, passes and read-backs
   static constexpr int kFieldBatch = 64;
@@ -2233,6 +2321,67 @@ int mmadmm_field_hessian_device(mmadmm_handle h, const double* d_u, double* d_H,
   return guarded([&] {
     if (!d_u || !d_H) throw Error(MMADMM_ERR_INVALID, "mmadmm_field_hessian_device: NULL array");
     eng(h).fieldHessian(d_u, d_H, true, stream);
+  });
+}
+// the weights of the components as the kernels take them: NULL is all 1.0
+static std::vector<double> check_fields(const char* who, int C, const double* U, const double* w) {
+  if (C < 1 || C > mmx::kFieldsMaxC)
+    throw Error(MMADMM_ERR_INVALID, std::string(who) + ": C must be 1 .. " + std::to_string(mmx::kFieldsMaxC));
+  if (!U) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": U is NULL");
+  std::vector<double> ws((size_t)C, 1.0);
+  for (int c = 0; w && c < C; ++c) {
+    if (!(std::isfinite(w[c]) && w[c] > 0))
+      throw Error(MMADMM_ERR_INVALID, std::string(who) + ": every weight must be finite and > 0");
+    ws[c] = w[c];
+  }
+  return ws;
+}
+int mmadmm_regrid_fields(mmadmm_handle h, int C, const double* U, const double* w, double alpha) {
+  return guarded([&] {
+    const std::vector<double> ws = check_fields("mmadmm_regrid_fields", C, U, w);
+    check_alpha("mmadmm_regrid_fields", alpha);
+    eng(h).regridFromFields(mmx::kMonFields, U, C, ws.data(), false, alpha, nullptr);
+  });
+}
+int mmadmm_regrid_fields_device(mmadmm_handle h, int C, const double* d_U, const double* w, double alpha,
+                                void* producer_stream) {
+  return guarded([&] {
+    const std::vector<double> ws = check_fields("mmadmm_regrid_fields_device", C, d_U, w);
+    check_alpha("mmadmm_regrid_fields_device", alpha);
+    eng(h).regridFromFields(mmx::kMonFields, d_U, C, ws.data(), true, alpha, producer_stream);
+  });
+}
+int mmadmm_regrid_fields_huang(mmadmm_handle h, int C, const double* U, const double* w, double alpha,
+                               double* alpha_used) {
+  return guarded([&] {
+    const std::vector<double> ws = check_fields("mmadmm_regrid_fields_huang", C, U, w);
+    check_alpha_huang("mmadmm_regrid_fields_huang", alpha);
+    eng(h).regridFromFields(mmx::kMonFieldsHuang, U, C, ws.data(), false, alpha, nullptr);
+    if (alpha_used) *alpha_used = eng(h).fieldAlphaUsed();
+  });
+}
+int mmadmm_regrid_fields_huang_device(mmadmm_handle h, int C, const double* d_U, const double* w, double alpha,
+                                      void* producer_stream, double* alpha_used) {
+  return guarded([&] {
+    const std::vector<double> ws = check_fields("mmadmm_regrid_fields_huang_device", C, d_U, w);
+    check_alpha_huang("mmadmm_regrid_fields_huang_device", alpha);
+    eng(h).regridFromFields(mmx::kMonFieldsHuang, d_U, C, ws.data(), true, alpha, producer_stream);
+    if (alpha_used) *alpha_used = eng(h).fieldAlphaUsed();
+  });
+}
+int mmadmm_field_hessians(mmadmm_handle h, int C, const double* U, const double* w, double* H, double* A) {
+  return guarded([&] {
+    const std::vector<double> ws = check_fields("mmadmm_field_hessians", C, U, w);
+    if (!H && !A) throw Error(MMADMM_ERR_INVALID, "mmadmm_field_hessians: H and A are both NULL");
+    eng(h).fieldHessians(U, C, ws.data(), H, A, false, nullptr);
+  });
+}
+int mmadmm_field_hessians_device(mmadmm_handle h, int C, const double* d_U, const double* w, double* d_H, double* d_A,
+                                 void* stream) {
+  return guarded([&] {
+    const std::vector<double> ws = check_fields("mmadmm_field_hessians_device", C, d_U, w);
+    if (!d_H && !d_A) throw Error(MMADMM_ERR_INVALID, "mmadmm_field_hessians_device: d_H and d_A are both NULL");
+    eng(h).fieldHessians(d_U, C, ws.data(), d_H, d_A, true, stream);
   });
 }
 static void check_transfer(const char* who, const double* Xold, int C, const double* uold, const double* unew) {

@@ -2,8 +2,11 @@
 // monitor of a nodal scalar field on the host (no device needed), compiled from the very text the
 // device kernels run (kernels/field_math.h; DESIGN.md §Monitor from a nodal field): bit-identical to
 // mmadmm_field_hessian / mmadmm_regrid_field / mmadmm_regrid_field_huang at the same positions and
-// simplices.
+// simplices.  mmadmm_fields_monitor is the same for several components: the twin of
+// mmadmm_field_hessians / mmadmm_regrid_fields / mmadmm_regrid_fields_huang.
+#include <algorithm>
 #include <cmath>
+#include <string>
 #include <vector>
 
 #include "../kernels/field_math.h"
@@ -84,6 +87,20 @@ double field_sum_host(int nP, ValueFn value) {
   return fin_sum_host(part);
 }
 
+// the device's search (field_math.h: field_solve_*) over l (nP x D) and om (nP), sum by sum
+template <int D>
+double field_solve_host(int nP, const std::vector<double>& l, const std::vector<double>& om) {
+  double Lambda = 0.0;
+  for (size_t i = 0; i < l.size(); ++i) Lambda = l[i] > Lambda ? l[i] : Lambda;
+  FieldSolve st{};
+  field_solve_begin(&st, field_sum_host(nP, [&](int v) { return om[v]; }), Lambda);
+  while (st.phase != kFieldDone)
+    field_solve_advance(&st, field_sum_host(nP, [&](int v) {
+                          return om[v] * field_huang_rho<D>(&l[(size_t)v * D], st.trial, nullptr);
+                        }));
+  return st.alpha;
+}
+
 template <int D>
 double field_monitor_huang_host(int nP, const double* X, int nF, const int32_t* F, const double* u, double alpha,
                                 double* H, double* M) {
@@ -92,17 +109,41 @@ double field_monitor_huang_host(int nP, const double* X, int nF, const int32_t* 
   field_recover_host<D>(nP, X, nF, F, u, [&](int v, const double* G, double sw) {
     field_huang_node<D>(G, sw, H ? H + (size_t)v * DD : nullptr, &A[(size_t)v * DD], &l[(size_t)v * D], &om[v]);
   });
-  if (!(alpha > 0.0)) {  // the device's search (field_math.h: field_solve_*), sum by sum
-    double Lambda = 0.0;
-    for (size_t i = 0; i < l.size(); ++i) Lambda = l[i] > Lambda ? l[i] : Lambda;
-    FieldSolve st{};
-    field_solve_begin(&st, field_sum_host(nP, [&](int v) { return om[v]; }), Lambda);
-    while (st.phase != kFieldDone)
-      field_solve_advance(&st, field_sum_host(nP, [&](int v) {
-                            return om[v] * field_huang_rho<D>(&l[(size_t)v * D], st.trial, nullptr);
-                          }));
-    alpha = st.alpha;
+  if (!(alpha > 0.0)) alpha = field_solve_host<D>(nP, l, om);
+  if (M)
+    for (int v = 0; v < nP; ++v) field_huang_monitor<D>(&A[(size_t)v * DD], &l[(size_t)v * D], alpha, M + (size_t)v * DD);
+  return alpha;
+}
+
+// the metric of C components: field_recover_host per column, the kernels' accumulation
+// text; H nP x C x D*D, A and M nP x D*D, each may be null.  Returns the alpha M was (or would be) built with
+template <int D>
+double fields_monitor_host(int nP, const double* X, int nF, const int32_t* F, int C, const double* U, const double* w,
+                           double alpha, bool normalise, double* H, double* Aout, double* M) {
+  constexpr int DD = D * D;
+  std::vector<double> A((size_t)nP * DD), om(nP), uc(nP);
+  for (int c = 0; c < C; ++c) {
+    for (int v = 0; v < nP; ++v) uc[v] = U[(size_t)v * C + c];
+    field_recover_host<D>(nP, X, nF, F, uc.data(), [&](int v, const double* G, double sw) {
+      double h[DD], ab[DD];
+      field_symmetrise<D>(G, h);
+      if (H)
+        for (int i = 0; i < DD; ++i) H[((size_t)v * C + c) * DD + i] = h[i];
+      field_abs_sym<D>(h, ab);
+      double* Av = &A[(size_t)v * DD];
+      field_accumulate<D>(ab, w ? w[c] : 1.0, c == 0, Av, Av);
+      om[v] = sw / (double)(D + 1);
+    });
   }
+  if (Aout) std::copy(A.begin(), A.end(), Aout);
+  if (!normalise) {
+    if (M)
+      for (int v = 0; v < nP; ++v) field_plain_monitor<D>(&A[(size_t)v * DD], alpha, M + (size_t)v * DD);
+    return alpha;
+  }
+  std::vector<double> l((size_t)nP * D);
+  for (int v = 0; v < nP; ++v) field_metric_diag<D>(&A[(size_t)v * DD], &l[(size_t)v * D]);
+  if (!(alpha > 0.0)) alpha = field_solve_host<D>(nP, l, om);
   if (M)
     for (int v = 0; v < nP; ++v) field_huang_monitor<D>(&A[(size_t)v * DD], &l[(size_t)v * D], alpha, M + (size_t)v * DD);
   return alpha;
@@ -141,6 +182,28 @@ extern "C" int mmadmm_field_monitor_huang(int dim, int nP, const double* Xp, int
       if (F[i] < 0 || F[i] >= nP) throw mmx::Error(MMADMM_ERR_INVALID, "simplex vertex id out of range");
     const double a = dim == 2 ? mmx::field_monitor_huang_host<2>(nP, Xp, nF, F, u, alpha, H, M)
                               : mmx::field_monitor_huang_host<3>(nP, Xp, nF, F, u, alpha, H, M);
+    if (alpha_used) *alpha_used = a;
+  });
+}
+
+extern "C" int mmadmm_fields_monitor(int dim, int nP, const double* Xp, int nF, const int32_t* F, int C,
+                                     const double* U, const double* w, double alpha, int normalise,
+                                     double* alpha_used, double* H, double* A, double* M) {
+  return mmx::guarded([&] {
+    const char* who = "mmadmm_fields_monitor";
+    if (C < 1 || C > 32) throw mmx::Error(MMADMM_ERR_INVALID, std::string(who) + ": C must be 1 .. 32");
+    mmx::check_field_arrays(who, dim, nP, Xp, nF, F, U);
+    for (int c = 0; w && c < C; ++c)
+      if (!(std::isfinite(w[c]) && w[c] > 0))
+        throw mmx::Error(MMADMM_ERR_INVALID, std::string(who) + ": every weight must be finite and > 0");
+    if (M && normalise && !(std::isfinite(alpha) && alpha >= 0))
+      throw mmx::Error(MMADMM_ERR_INVALID, std::string(who) + ": alpha must be finite and > 0, or 0 (solved)");
+    if (M && !normalise && !(std::isfinite(alpha) && alpha > 0))
+      throw mmx::Error(MMADMM_ERR_INVALID, std::string(who) + ": alpha must be finite and > 0");
+    for (long long i = 0; i < (long long)nF * (dim + 1); ++i)
+      if (F[i] < 0 || F[i] >= nP) throw mmx::Error(MMADMM_ERR_INVALID, "simplex vertex id out of range");
+    const double a = dim == 2 ? mmx::fields_monitor_host<2>(nP, Xp, nF, F, C, U, w, alpha, normalise != 0, H, A, M)
+                              : mmx::fields_monitor_host<3>(nP, Xp, nF, F, C, U, w, alpha, normalise != 0, H, A, M);
     if (alpha_used) *alpha_used = a;
   });
 }

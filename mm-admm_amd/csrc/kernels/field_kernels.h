@@ -42,4 +42,21 @@ template <int D>
 void launch_field_huang_final(const double* absH, const double* lw, int nP, const FieldSolve* state, double* M,
                               hipStream_t st);
 
+// The metric of C components: U nP x C row-major, w C host weights.  First recovery in
+// batches of up to D components (positions and simplex geometry gathered once per batch), each
+// component's gradient into its plane of `planes` (C x nP x D); then per component the second
+// recovery and a node pass that stores H_c (H: nP x C x D*D, may be null) and accumulates
+// A = sum_c w_c |H_c| in ascending c (A: nP x D*D, may be null when only H is wanted).
+// 2 ceil(C / D) + 2 C launches.  fin ends the metric in the last component's launch:
+//   kFieldsNone   A holds the metric
+//   kFieldsPlain  A holds M = I + metric / alpha instead
+//   kFieldsHuang  A holds the metric and lw ((D + 1) x nP) {l, omega} as launch_field_huang_recover
+//                 leaves them: launch_field_solve_* and launch_field_huang_final follow unchanged
+enum FieldsFinal { kFieldsNone = 0, kFieldsPlain = 1, kFieldsHuang = 2 };
+constexpr int kFieldsMaxC = 32;
+template <int D>
+void launch_fields_recover(const double* X, const double* U, int C, const double* w, const int* F, int nF,
+                           const int* incPtr, const int* incOff, const int* nodeOrder, int nP, double* ebuf,
+                           double* planes, double* H, double* A, int fin, double alpha, double* lw, hipStream_t st);
+
 }  // namespace mmx

@@ -17,6 +17,8 @@
 //             t = sqrt(c); 3D: s = root7(d), rho = s s, t = s; M_ij = (delta_ij + |H|_ij / alpha) / t, so
 //             sqrt(det M) = rho; omega_v = (sum_s w_s) / (D + 1); alpha given, or solved from
 //             sum_v omega_v rho_v(alpha) = 2 sum_v omega_v (field_solve_*)
+//   several   components: A = w_0 |H_0| + w_1 |H_1| + ... in ascending order from the
+//             first product, in the place of |H| above; Huang's l is the Jacobi diagonal of A
 #pragma once
 
 #if defined(__HIPCC__)
@@ -38,17 +40,18 @@ constexpr int field_elem_stride(int C) {
 
 MMX_FHD double field_abs(double x) { return x < 0.0 ? -x : x; }
 
-// one simplex: f = its D + 1 vertex ids, X positions (n x D), val values (n x C, C components
-// per vertex); out = {w, g[C][D]}
+// one simplex: f = its D + 1 vertex ids, X positions (n x D), val values (C components per vertex,
+// vertex v's at val[v ld .. v ld + C): ld >= C, so a batch of C columns of a wider array can be read
+// in place); out = {w, g[C][D]}
 template <int D, int C>
-MMX_FHD void field_element(const double* X, const double* val, const int* f, double* out) {
+MMX_FHD void field_element_ld(const double* X, const double* val, int ld, const int* f, double* out) {
   double e[D][D], du[D][C];
 #pragma unroll
   for (int j = 0; j < D; ++j) {
 #pragma unroll
     for (int k = 0; k < D; ++k) e[j][k] = X[(size_t)f[j + 1] * D + k] - X[(size_t)f[0] * D + k];
 #pragma unroll
-    for (int c = 0; c < C; ++c) du[j][c] = val[(size_t)f[j + 1] * C + c] - val[(size_t)f[0] * C + c];
+    for (int c = 0; c < C; ++c) du[j][c] = val[(size_t)f[j + 1] * ld + c] - val[(size_t)f[0] * ld + c];
   }
   if (D == 2) {
     const double det = e[0][0] * e[1][1] - e[0][1] * e[1][0];
@@ -77,6 +80,12 @@ MMX_FHD void field_element(const double* X, const double* val, const int* f, dou
       for (int k = 0; k < 3; ++k)
         out[1 + c * D + k] = ((du[0][c] * cr[0][k] + du[1][c] * cr[1][k]) + du[2][c] * cr[2][k]) / det;
   }
+}
+
+// val n x C: C components per vertex, nothing between them
+template <int D, int C>
+MMX_FHD void field_element(const double* X, const double* val, const int* f, double* out) {
+  field_element_ld<D, C>(X, val, C, f, out);
 }
 
 // one node: off[0 .. cnt) its incident slot offsets s K + n D in ascending simplex id (the
@@ -239,6 +248,27 @@ MMX_FHD void field_epilogue(const double* G, double alpha, double* H, double* M)
 #pragma unroll
     for (int i = 0; i < D * D; ++i) M[i] = ((i / D == i % D) ? 1.0 : 0.0) + ab[i] / alpha;
   }
+}
+
+// ---- several components ------------------------------------------------------------
+// the combined metric A = w_0 |H_0| + w_1 |H_1| + ..., one component per call in ascending c: the sum
+// starts from its first product (first: Ain is not read), every product rounded before it is added
+template <int D>
+MMX_FHD void field_accumulate(const double* absH, double w, bool first, const double* Ain, double* Aout) {
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) Aout[i] = first ? w * absH[i] : Ain[i] + w * absH[i];
+}
+// M = I + A / alpha
+template <int D>
+MMX_FHD void field_plain_monitor(const double* A, double alpha, double* M) {
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) M[i] = ((i / D == i % D) ? 1.0 : 0.0) + A[i] / alpha;
+}
+// l_k = |a_kk| of the Jacobi on the combined metric A (field_abs_sym's l; its re-assembly is not used)
+template <int D>
+MMX_FHD void field_metric_diag(const double* A, double* l) {
+  double re[D * D];
+  field_abs_sym<D>(A, re, l);
 }
 
 // ---- Huang's normalised monitor ----------------------------------------------------------------

@@ -127,6 +127,19 @@ def lib():
     L.mmadmm_field_monitor_huang.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_int_p, c_double_p,
                                              ctypes.c_double, c_double_p, c_double_p, c_double_p]
     L.mmadmm_field_root.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p]
+    L.mmadmm_regrid_fields.argtypes = [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, ctypes.c_double]
+    L.mmadmm_regrid_fields_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, c_double_p,
+                                              ctypes.c_double, ctypes.c_void_p]
+    L.mmadmm_regrid_fields_huang.argtypes = [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, ctypes.c_double,
+                                             c_double_p]
+    L.mmadmm_regrid_fields_huang_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, c_double_p,
+                                                    ctypes.c_double, ctypes.c_void_p, c_double_p]
+    L.mmadmm_field_hessians.argtypes = [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p]
+    L.mmadmm_field_hessians_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, c_double_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.mmadmm_fields_monitor.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_int_p, ctypes.c_int,
+                                        c_double_p, c_double_p, ctypes.c_double, ctypes.c_int, c_double_p, c_double_p,
+                                        c_double_p, c_double_p]
     L.mmadmm_transfer.argtypes = [ctypes.c_void_p, c_double_p, c_double_p, ctypes.c_int, c_double_p, c_double_p,
                                   c_int_p, c_int_p]
     L.mmadmm_transfer_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
@@ -268,6 +281,56 @@ def field_monitor_huang(Xp, F, u, alpha=None):
                                             0.0 if alpha is None else float(alpha), ctypes.byref(used), _dp(H),
                                             _dp(M)))
     return H, M, used.value
+
+
+def _weights(weights, C, who):
+    """the C weights as a float64 array, or None for all 1.0"""
+    if weights is None:
+        return None
+    w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if w.size != C:
+        raise ValueError(f"{who}: {C} components, {w.size} weights")
+    return w
+
+
+def _mean_frobenius(A):
+    """the default alpha of the plain monitor: the mean Frobenius norm of A (1.0 when that is 0)"""
+    if _is_tensor(A):
+        alpha = float((A * A).sum(dim=(1, 2)).sqrt().mean())
+    else:
+        alpha = float(np.sqrt((A * A).sum(axis=(1, 2))).mean())
+    return 1.0 if alpha == 0.0 else alpha
+
+
+def fields_monitor(Xp, F, U, weights=None, alpha=None, normalise=False):
+    """mmadmm_fields_monitor (host only, no device): the monitor from several components.  U: nP x C
+    (nP values: C = 1); H_c the recovered Hessian of column c, A = sum_c weights[c] |H_c| (weights None:
+    all 1), M = I + A / alpha, or with normalise Huang's (I + A / alpha) / t -> (H, A, M, alpha_used),
+    H nP x C x D x D, A and M nP x D x D.  alpha None: the mean Frobenius norm of A (1.0 when that is 0),
+    or with normalise solved from the equidistribution equation.  Bit-identical to Engine.field_hessians
+    and Engine.regrid_fields with F = Engine.simplices()."""
+    Xp = np.ascontiguousarray(Xp, dtype=np.float64)
+    F = np.ascontiguousarray(F, dtype=np.int32)
+    if Xp.ndim != 2 or F.ndim != 2 or F.shape[1] != Xp.shape[1] + 1:
+        raise ValueError("fields_monitor: Xp nP x D, F nF x (D + 1)")
+    nP, D = Xp.shape
+    U = _field_2d(U, nP, "fields_monitor")
+    C = U.shape[1]
+    w = _weights(weights, C, "fields_monitor")
+    H, A, M = np.zeros((nP, C, D, D)), np.zeros((nP, D, D)), np.zeros((nP, D, D))
+    used = ctypes.c_double(0.0)
+
+    def call(a, h, m):
+        _check(lib().mmadmm_fields_monitor(D, nP, _dp(Xp), F.shape[0], _ip(F), C, _dp(U),
+                                           _dp(w) if w is not None else None, a, 1 if normalise else 0,
+                                           ctypes.byref(used), _dp(H) if h else None, _dp(A), _dp(M) if m else None))
+
+    if alpha is None and not normalise:
+        call(1.0, True, False)
+        call(_mean_frobenius(A), False, True)
+    else:
+        call(0.0 if alpha is None else float(alpha), True, True)
+    return H, A, M, used.value
 
 
 TRANSFER_COUNTS = ("copied", "patch", "walked", "outside")
@@ -919,9 +982,74 @@ class Engine:
         _check(lib().mmadmm_regrid_field(self.h, _dp(u), alpha))
         return alpha
 
+    def _fields_arg(self, U, weights, who):
+        """(is tensor, U as the call takes it, C, weights pointer or None, the weights array kept alive)"""
+        if _is_tensor(U):
+            if U.dim() not in (1, 2) or U.shape[0] != self.nP or U.numel() == 0:
+                raise ValueError(f"{who}: U must be nP or nP x C values (C >= 1), nP = {self.nP}")
+            C = U.numel() // self.nP
+            tensor = True
+        else:
+            U = _field_2d(U, self.nP, who)
+            C = U.shape[1]
+            tensor = False
+        w = _weights(weights, C, who)
+        return tensor, U, C, (_dp(w) if w is not None else None), w
+
+    def field_hessians(self, U, weights=None):
+        """The recovered Hessians of the C components of U (nP x C; nP values: C = 1) on the current mesh
+        and their metric A = sum_c weights[c] |H_c| (weights None: all 1; include/mmadmm.h:
+        mmadmm_field_hessians) -> (H, A), nP x C x D x D and nP x D x D: tensors for a tensor, arrays for
+        an array."""
+        tensor, U, C, wp, w = self._fields_arg(U, weights, "field_hessians")
+        D = self.dim
+        if tensor:
+            import torch
+
+            p, st, j = self._device_arg(U, self.nP * C, "field_hessians")
+            H = torch.empty((self.nP, C, D, D), dtype=torch.float64, device=U.device)
+            A = torch.empty((self.nP, D, D), dtype=torch.float64, device=U.device)
+            if j is not None:
+                H.record_stream(j[1])
+                A.record_stream(j[1])
+            _check(lib().mmadmm_field_hessians_device(self.h, C, p, wp, H.data_ptr(), A.data_ptr(), st))
+            self._rejoin(j)
+            return H, A
+        H, A = np.zeros((self.nP, C, D, D)), np.zeros((self.nP, D, D))
+        _check(lib().mmadmm_field_hessians(self.h, C, _dp(U), wp, _dp(H), _dp(A)))
+        return H, A
+
+    def regrid_fields(self, U, weights=None, alpha=None, normalise=False):
+        """Rebuild the monitor grid from the C components of U (nP x C; nP values: C = 1): M = I + A / alpha,
+        A = sum_c weights[c] |H_c| the sum of the components' absolute Hessians (weights None: all 1).
+        alpha None: the mean Frobenius norm of A (1.0 when that is 0).  normalise=True: Huang's metric
+        (I + A / alpha) / t, and alpha None is solved on the device (include/mmadmm.h:
+        mmadmm_regrid_fields, mmadmm_regrid_fields_huang).  Returns the alpha used."""
+        tensor, U, C, wp, w = self._fields_arg(U, weights, "regrid_fields")
+        if normalise:
+            used = ctypes.c_double(0.0)
+            alpha = 0.0 if alpha is None else float(alpha)
+            if tensor:
+                p, st, j = self._device_arg(U, self.nP * C, "regrid_fields")
+                _check(lib().mmadmm_regrid_fields_huang_device(self.h, C, p, wp, alpha, st, ctypes.byref(used)))
+                self._rejoin(j)
+            else:
+                _check(lib().mmadmm_regrid_fields_huang(self.h, C, _dp(U), wp, alpha, ctypes.byref(used)))
+            return used.value
+        if alpha is None:
+            alpha = _mean_frobenius(self.field_hessians(U, w)[1])
+        alpha = float(alpha)
+        if tensor:
+            p, st, j = self._device_arg(U, self.nP * C, "regrid_fields")
+            _check(lib().mmadmm_regrid_fields_device(self.h, C, p, wp, alpha, st))
+            self._rejoin(j)
+        else:
+            _check(lib().mmadmm_regrid_fields(self.h, C, _dp(U), wp, alpha))
+        return alpha
+
     def field_solve_info(self):
-        """(sums evaluated, state read-backs) of the last regrid_field(..., normalise=True) that solved
-        alpha; (0, 0) after a given alpha."""
+        """(sums evaluated, state read-backs) of the last regrid_field / regrid_fields(..., normalise=True)
+        that solved alpha; (0, 0) after a given alpha."""
         passes, syncs = ctypes.c_int(0), ctypes.c_int(0)
         _check(lib().mmadmm_field_solve_info(self.h, ctypes.byref(passes), ctypes.byref(syncs)))
         return passes.value, syncs.value
