@@ -297,6 +297,58 @@ int mmadmm_quality_device(mmadmm_handle h, const double* d_X, int source, const 
 int mmadmm_mesh_quality(int dim, int nP, const double* Xp, const double* Xc, int nF, const int32_t* F,
                         const double* Ehat, const double* M, double* q, double* summary);
 
+/* ---- sliding boundary: BOUNDARY_FREE nodes kept on the domain's surface
+ * The reference's Mesh<D>::projectOntoBoundary (src/Mesh.cpp:118-241) is never called (the call in
+ * updateAfterStep is commented out, src/Mesh.cpp:1020-1026), so a BOUNDARY_FREE node moves like an
+ * interior one and leaves the surface.  With sliding on, mmadmm_step ends by projecting every sliding
+ * node of x onto the frozen boundary surface, on the device, before "points" takes x.  Off by
+ * default; with it off nothing changes.  mmadmm_euler_step and mmadmm_backward_euler_step move
+ * INTERIOR nodes only: there is nothing to project there.
+ *   surface   frozen at the first mmadmm_set_boundary_slide(h, 1) (again by mmadmm_boundary_refreeze)
+ *             from the engine's current "points" X0 and the simplices of mmadmm_get_simplices: the
+ *             faces with no neighbour (mmadmm_face_neighbours), ids ascending with (simplex, local
+ *             opposite vertex), each face's vertices the simplex's other vertices in local order.
+ *             The projection is always onto this surface at X0, never onto the nodes' current chords
+ *   sliding   a BOUNDARY_FREE node on at least one boundary face; it carries an anchor, a vertex of
+ *             the surface, initially itself, kept from call to call
+ *   project   over the faces at the anchor (ascending id) the closest point with the smallest squared
+ *             distance d2 (the first wins ties) replaces the best so far when it is smaller; then the
+ *             anchor hops to that face's vertex with the largest barycentric weight, unless that is
+ *             the anchor itself or BOUNDARY_FIXED (a node never passes a pinned vertex), at most 8
+ *             hops.  The node takes the best point.  A position with a NaN finds no face: the node and
+ *             its anchor stay as they are (counted unmoved)
+ * counts (5 host ints): {unmoved: the result has the position's bits; star / hopped: moved, with no
+ * hop / at least one; exhausted: the hop limit ended the search (whatever it found); at_pin, counted
+ * beside the other four: the result has the bits of a BOUNDARY_FIXED vertex of its face}.  max_d2:
+ * the largest d2 of the call.  Integer adds and an integer maximum of the bit pattern: reproducible.
+ * mmadmm_project_boundary projects the caller's positions X (nP x D host doubles, in place) through
+ * the same kernel; the _device form takes a device array ordered after `stream`'s work and hands it
+ * back to that stream with no host synchronisation unless counts or max_d2 is asked for (stream NULL:
+ * the data are ready, and the call returns when the results are).  Both use and advance the engine's
+ * anchors: they are for callers that move nodes themselves.  mmadmm_slide_counts: the figures of the
+ * last step's projection (zeros when no step has projected yet); asking costs one small read-back, a
+ * step never reads back on its own.  mmadmm_boundary_info: the frozen faces (nFaces x D), the sliding
+ * node ids (nSliding, ascending) and their anchors; every pointer may be NULL.
+ * Refused (MMADMM_ERR_INVALID): an element partition (single rank only), on outside {0, 1}, a NULL X,
+ * and info, project, refreeze or counts before any freeze.  Two sliding nodes that cross invert an
+ * element; the next step's prox reports it, as for any other inverted element. */
+int mmadmm_set_boundary_slide(mmadmm_handle h, int on);
+int mmadmm_boundary_refreeze(mmadmm_handle h);
+int mmadmm_boundary_info(mmadmm_handle h, int* nFaces, int* nSliding, int32_t* faces, int32_t* sliding,
+                         int32_t* anchors);
+int mmadmm_project_boundary(mmadmm_handle h, double* X, int* counts, double* max_d2);
+int mmadmm_project_boundary_device(mmadmm_handle h, double* d_X, void* stream, int* counts, double* max_d2);
+int mmadmm_slide_counts(mmadmm_handle h, int* counts, double* max_d2);
+/* Host only, no device needed: the same projection on the CPU in the kernel's arithmetic, on
+ * stand-alone arrays: the surface of (F, mask) frozen at X0 (bit-identical to the calls above with
+ * F = mmadmm_get_simplices' simplices: F is used as given).  anchor (nP ints, entry v the anchor of
+ * node v; only the sliding nodes' entries are read and written) and X (nP x dim) are updated in
+ * place.  Refused: X == X0, a sliding node's anchor that is no vertex of the surface. */
+int mmadmm_boundary_project_field(int dim, int nP, const double* X0, int nF, const int32_t* F, const int32_t* mask,
+                                  int32_t* anchor, double* X, int* counts, double* max_d2);
+/* The boundary faces of F as above (host only): *nFaces, and faces (nFaces x dim) when not NULL. */
+int mmadmm_boundary_faces(int dim, int nP, int nF, const int32_t* F, int* nFaces, int32_t* faces);
+
 const char* mmadmm_last_error(void);
 int mmadmm_version(void);
 /* provenance (no reference counterpart): "src_hash=<16 hex> git=<describe> arch=gfx950", the hash of

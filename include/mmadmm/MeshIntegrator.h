@@ -138,6 +138,17 @@ public:
         mmadmm_cxx::check(onDevice ? mmadmm_quality_device(h_, X, source, M, q, summary, nullptr)
                                    : mmadmm_quality(h_, X, source, M, q, summary));
     }
+    // BOUNDARY_FREE nodes slide on the boundary: every step() ends by projecting them onto the boundary
+    // surface frozen at the first setBoundarySliding(true), on the device -- the reference's
+    // Mesh<D>::projectOntoBoundary, whose call in updateAfterStep is commented out (src/Mesh.cpp:1020-1026).
+    // Off by default.  projectOntoBoundary projects the caller's positions X (nP x D row-major, in place)
+    // with the engine's anchors; onDevice: X is in device memory and ready (include/mmadmm.h:
+    // mmadmm_set_boundary_slide, mmadmm_project_boundary and its _device form)
+    void setBoundarySliding(bool on) { mmadmm_cxx::check(mmadmm_set_boundary_slide(h_, on ? 1 : 0)); }
+    void projectOntoBoundary(double *X, bool onDevice = false) {
+        mmadmm_cxx::check(onDevice ? mmadmm_project_boundary_device(h_, X, nullptr, nullptr, nullptr)
+                                   : mmadmm_project_boundary(h_, X, nullptr, nullptr));
+    }
     // the engine behind this integrator, for the C-ABI calls the reference's class has no name for
     mmadmm_handle handle() const { return h_; }
 

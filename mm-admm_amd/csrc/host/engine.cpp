@@ -18,10 +18,12 @@
 #include "../kernels/field_kernels.h"
 #include "../kernels/quality_kernels.h"
 #include "../kernels/regrid_kernels.h"
+#include "../kernels/slide_kernels.h"
 #include "../kernels/transfer_kernels.h"
 #include "comm.h"
 #include "common.h"
 #include "partition.h"
+#include "slide.h"
 #include "transfer.h"
 #include "xup_records.h"
 
@@ -80,6 +82,12 @@ struct EngineBase {
   // mmadmm_quality(_device): Huang's measures of the mesh at X (null: Vp) against the monitor `source`
   virtual void quality(const double* X, int source, const double* M, double* q, double* summary, bool onDevice,
                        void* stream) = 0;
+  // the sliding boundary (mmadmm_set_boundary_slide ... mmadmm_slide_counts)
+  virtual void setBoundarySlide(int on) = 0;
+  virtual void boundaryRefreeze() = 0;
+  virtual void boundaryInfo(int* nFaces, int* nSliding, int32_t* faces, int32_t* sliding, int32_t* anchors) = 0;
+  virtual void projectBoundary(double* X, int* counts, double* maxD2, bool onDevice, void* stream) = 0;
+  virtual void slideCounts(int* counts, double* maxD2) = 0;
   virtual void debugBlockGrad(int s, const double* z, const double* dx, int flags, double* out) = 0;
   virtual std::string options() const = 0;
 };
@@ -502,7 +510,14 @@ class Engine final : public EngineBase {
         if (r[4] > 0 || (primal < tol && dual < tol)) break;
       }
     }
-    // Mesh::updateAfterStep: Vp = x
+    // Mesh::updateAfterStep: the sliding nodes back onto the frozen boundary (the reference's
+    // commented-out projectOntoBoundary call, src/Mesh.cpp:1020-1026), then Vp = x.  The next step
+    // restarts z = D x from these positions
+    if (slideOn_ && !slS_.sliding.empty()) {
+      launch_slide_project<D>(slX0_.p, slFaces_.p, slStarPtr_.p, slStarFace_.p, slMask_.p, slIds_.p,
+                              (int)slS_.sliding.size(), x_.p, slAnchor_.p, slStepCnt_.p, st_);
+      slStepValid_ = true;
+    }
     MMX_HIP(hipMemcpyAsync(Vp_.p, x_.p, (size_t)nP_ * D * sizeof(double), hipMemcpyDeviceToDevice, st_));
     vpVersion_++;
     if (timing) {
@@ -1349,6 +1364,109 @@ class Engine final : public EngineBase {
     if (summary) std::memcpy(summary, qlRecH_, 8 * sizeof(double));
   }
 
+  // ---- the sliding boundary (slide_kernels.hip)
+  // the surface frozen at the current points: faces, the CSR of faces at every node, the sliding
+  // nodes and their anchors (each its own node), uploaded once per freeze
+  void slideFreeze() {
+    std::vector<int32_t> maskL(nP_);
+    for (int v = 0; v < nP_; ++v) maskL[v] = maskH_[plan_.localNodes[v]];
+    build_slide_surface(D, nP_, nF_, plan_.Flocal.data(), maskL.data(), slS_);
+    static const int32_t none[1] = {0};
+    auto up = [&](DevBuf<int32_t>& b, const std::vector<int32_t>& h) {
+      b.upload(h.empty() ? none : h.data(), std::max<size_t>(h.size(), 1), st_);
+    };
+    slX0_.alloc((size_t)nP_ * D);
+    MMX_HIP(hipMemcpyAsync(slX0_.p, Vp_.p, (size_t)nP_ * D * sizeof(double), hipMemcpyDeviceToDevice, st_));
+    up(slFaces_, slS_.faces);
+    up(slStarPtr_, slS_.starPtr);
+    up(slStarFace_, slS_.starFace);
+    up(slMask_, maskL);
+    up(slIds_, slS_.sliding);
+    up(slAnchor_, slS_.sliding);
+    if (!slCnt_.p) {
+      slCnt_.alloc(kSlideCountInts);
+      slStepCnt_.alloc(kSlideCountInts);
+    }
+    streamWait();
+    slStepValid_ = false;
+    slFrozen_ = true;
+  }
+  void slideFrozenOnly(const char* who) const {
+    singleRankOnly(who);
+    if (!slFrozen_)
+      throw Error(MMADMM_ERR_INVALID, std::string(who) + ": no frozen boundary (call mmadmm_set_boundary_slide(h, 1) first)");
+  }
+  void setBoundarySlide(int on) override {
+    singleRankOnly("mmadmm_set_boundary_slide");
+    if (on != 0 && on != 1) throw Error(MMADMM_ERR_INVALID, "mmadmm_set_boundary_slide: on must be 0 or 1");
+    if (on && !slFrozen_) slideFreeze();
+    slideOn_ = on == 1;
+  }
+  void boundaryRefreeze() override {
+    slideFrozenOnly("mmadmm_boundary_refreeze");
+    slideFreeze();
+  }
+  void boundaryInfo(int* nFaces, int* nSliding, int32_t* faces, int32_t* sliding, int32_t* anchors) override {
+    slideFrozenOnly("mmadmm_boundary_info");
+    if (nFaces) *nFaces = slS_.nFaces;
+    if (nSliding) *nSliding = (int)slS_.sliding.size();
+    if (faces) std::copy(slS_.faces.begin(), slS_.faces.end(), faces);
+    if (sliding) std::copy(slS_.sliding.begin(), slS_.sliding.end(), sliding);
+    if (anchors && !slS_.sliding.empty()) {
+      MMX_HIP(hipMemcpyAsync(anchors, slAnchor_.p, slS_.sliding.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+      streamWait();
+    }
+  }
+  // mmadmm_project_boundary / mmadmm_project_boundary_device
+  void projectBoundary(double* X, int* counts, double* maxD2, bool onDevice, void* stream) override {
+    const char* who = onDevice ? "mmadmm_project_boundary_device" : "mmadmm_project_boundary";
+    slideFrozenOnly(who);
+    if (!X) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": NULL array");
+    const int nS = (int)slS_.sliding.size();
+    const bool want = counts || maxD2;
+    int cnt[kSlideCountInts];  // the slotted figures (slide_kernels.h), read back when asked for
+    if (nS == 0) {  // nothing slides: nothing is launched
+      std::memset(cnt, 0, sizeof cnt);
+    } else if (!onDevice) {  // staged through the same kernel; the host array is done with when the call returns
+      const size_t nx = (size_t)nP_ * D;
+      if (slStage_.n < nx) slStage_.alloc(nx);
+      MMX_HIP(hipMemcpyAsync(slStage_.p, X, nx * sizeof(double), hipMemcpyHostToDevice, st_));
+      launch_slide_project<D>(slX0_.p, slFaces_.p, slStarPtr_.p, slStarFace_.p, slMask_.p, slIds_.p, nS, slStage_.p,
+                              slAnchor_.p, want ? slCnt_.p : nullptr, st_);
+      MMX_HIP(hipGetLastError());
+      MMX_HIP(hipMemcpyAsync(X, slStage_.p, nx * sizeof(double), hipMemcpyDeviceToHost, st_));
+      if (want) MMX_HIP(hipMemcpyAsync(cnt, slCnt_.p, sizeof cnt, hipMemcpyDeviceToHost, st_));
+      streamWait();
+    } else {
+      afterProducer(stream);
+      launch_slide_project<D>(slX0_.p, slFaces_.p, slStarPtr_.p, slStarFace_.p, slMask_.p, slIds_.p, nS, X, slAnchor_.p,
+                              want ? slCnt_.p : nullptr, st_);
+      MMX_HIP(hipGetLastError());
+      if (want) MMX_HIP(hipMemcpyAsync(cnt, slCnt_.p, sizeof cnt, hipMemcpyDeviceToHost, st_));
+      beforeConsumer(stream);
+      if (want && stream) streamWait();  // the read-back; without the figures the host does not wait
+    }
+    if (want) {
+      int c5[5];
+      slide_fold_counts(cnt, c5, maxD2);
+      if (counts) std::copy(c5, c5 + 5, counts);
+    }
+  }
+  // mmadmm_slide_counts: the figures of the last step's projection
+  void slideCounts(int* counts, double* maxD2) override {
+    slideFrozenOnly("mmadmm_slide_counts");
+    int cnt[kSlideCountInts];
+    if (slStepValid_) {
+      MMX_HIP(hipMemcpyAsync(cnt, slStepCnt_.p, sizeof cnt, hipMemcpyDeviceToHost, st_));
+      streamWait();
+    } else {
+      std::memset(cnt, 0, sizeof cnt);
+    }
+    int c5[5];
+    slide_fold_counts(cnt, c5, maxD2);
+    if (counts) std::copy(c5, c5 + 5, counts);
+  }
+
   // mmadmm_get_device: "x" or "points" into the caller's device array
   void getDevice(const std::string& what, double* dOut, void* stream) override {
     singleRankOnly("mmadmm_get_device");
@@ -1989,6 +2107,12 @@ class Engine final : public EngineBase {
   DevBuf<int32_t> trNbr_, trWhere_, trCnt_;
   DevBuf<double> trStage_;
   DevBuf<double> qlE_, qlC_, qlPart_, qlRec_, qlStage_;  // the quality measures' scratch (qualityScratch)
+  // the sliding boundary: on / frozen, the frozen surface (host, device), the sliding nodes and their
+  // anchors, the slotted figures of a call and of the last step (slStepValid_: a step has written them)
+  bool slideOn_ = false, slFrozen_ = false, slStepValid_ = false;
+  SlideSurface slS_;
+  DevBuf<double> slX0_, slStage_;
+  DevBuf<int32_t> slFaces_, slStarPtr_, slStarFace_, slMask_, slIds_, slAnchor_, slCnt_, slStepCnt_;
   double* qlRecH_ = nullptr;
   const double* srcPtr_ = nullptr;
   double srcAlpha_ = 1.0;
@@ -2409,6 +2533,25 @@ int mmadmm_quality(mmadmm_handle h, const double* X, int source, const double* M
 int mmadmm_quality_device(mmadmm_handle h, const double* d_X, int source, const double* d_M, double* d_q,
                           double* summary, void* stream) {
   return guarded([&] { eng(h).quality(d_X, source, d_M, d_q, summary, true, stream); });
+}
+int mmadmm_set_boundary_slide(mmadmm_handle h, int on) {
+  return guarded([&] { eng(h).setBoundarySlide(on); });
+}
+int mmadmm_boundary_refreeze(mmadmm_handle h) {
+  return guarded([&] { eng(h).boundaryRefreeze(); });
+}
+int mmadmm_boundary_info(mmadmm_handle h, int* nFaces, int* nSliding, int32_t* faces, int32_t* sliding,
+                         int32_t* anchors) {
+  return guarded([&] { eng(h).boundaryInfo(nFaces, nSliding, faces, sliding, anchors); });
+}
+int mmadmm_project_boundary(mmadmm_handle h, double* X, int* counts, double* max_d2) {
+  return guarded([&] { eng(h).projectBoundary(X, counts, max_d2, false, nullptr); });
+}
+int mmadmm_project_boundary_device(mmadmm_handle h, double* d_X, void* stream, int* counts, double* max_d2) {
+  return guarded([&] { eng(h).projectBoundary(d_X, counts, max_d2, true, stream); });
+}
+int mmadmm_slide_counts(mmadmm_handle h, int* counts, double* max_d2) {
+  return guarded([&] { eng(h).slideCounts(counts, max_d2); });
 }
 int mmadmm_get_device(mmadmm_handle h, const char* what, double* d_out, void* consumer_stream) {
   return guarded([&] {

@@ -42,6 +42,13 @@ void build_face_neighbours(int D, int nF, const int32_t* F, int32_t* nbr) {
   }
 }
 
+void check_simplices(const char* who, int dim, int nP, int nF, const int32_t* F) {
+  if ((dim != 2 && dim != 3) || nP < 1 || nF < 0) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": bad dim / sizes");
+  if (nF > 0 && !F) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": NULL array");
+  for (long long i = 0; i < (long long)nF * (dim + 1); ++i)
+    if (F[i] < 0 || F[i] >= nP) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": simplex vertex id out of range");
+}
+
 namespace {
 
 template <int D>
@@ -85,13 +92,6 @@ void transfer_host(int nP, const double* Xold, int nF, const int32_t* F, const d
   }
   if (counts)
     for (int k = 0; k < 4; ++k) counts[k] = cnt[k];
-}
-
-void check_simplices(const char* who, int dim, int nP, int nF, const int32_t* F) {
-  if ((dim != 2 && dim != 3) || nP < 1 || nF < 0) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": bad dim / sizes");
-  if (nF > 0 && !F) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": NULL array");
-  for (long long i = 0; i < (long long)nF * (dim + 1); ++i)
-    if (F[i] < 0 || F[i] >= nP) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": simplex vertex id out of range");
 }
 
 }  // namespace

@@ -10,4 +10,8 @@ namespace mmx {
 // simplices share (not a manifold mesh) pairs its two lowest simplices; the others get -1.
 void build_face_neighbours(int D, int nF, const int32_t* F, int32_t* nbr);
 
+// throws MMADMM_ERR_INVALID ("<who>: ...") unless dim is 2 or 3, nP >= 1, nF >= 0, F is there when
+// nF > 0 and every vertex id lies in [0, nP)
+void check_simplices(const char* who, int dim, int nP, int nF, const int32_t* F);
+
 }  // namespace mmx

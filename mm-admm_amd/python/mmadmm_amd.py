@@ -152,6 +152,15 @@ def lib():
                                         ctypes.c_void_p, c_double_p, ctypes.c_void_p]
     L.mmadmm_mesh_quality.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_int_p,
                                       c_double_p, c_double_p, c_double_p, c_double_p]
+    L.mmadmm_set_boundary_slide.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.mmadmm_boundary_refreeze.argtypes = [ctypes.c_void_p]
+    L.mmadmm_boundary_info.argtypes = [ctypes.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p]
+    L.mmadmm_project_boundary.argtypes = [ctypes.c_void_p, c_double_p, c_int_p, c_double_p]
+    L.mmadmm_project_boundary_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_int_p, c_double_p]
+    L.mmadmm_slide_counts.argtypes = [ctypes.c_void_p, c_int_p, c_double_p]
+    L.mmadmm_boundary_project_field.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_int_p, c_int_p,
+                                                c_int_p, c_double_p, c_int_p, c_double_p]
+    L.mmadmm_boundary_faces.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, c_int_p, c_int_p]
     L.mmadmm_destroy.argtypes = [ctypes.c_void_p]
     L.mmadmm_mesh_rect.argtypes = [ctypes.c_int] * 4 + [ctypes.c_double] * 6 + [ctypes.c_int,
                                                                                  ctypes.POINTER(ctypes.c_void_p)]
@@ -377,6 +386,53 @@ def face_neighbours(F, nP=None):
     _check(lib().mmadmm_face_neighbours(F.shape[1] - 1, int(F.max()) + 1 if nP is None else nP, F.shape[0], _ip(F),
                                         _ip(nbr)))
     return nbr
+
+
+SLIDE_COUNTS = ("unmoved", "star", "hopped", "exhausted", "at_pin")
+
+
+def _slide_info(cnt, mx):
+    info = {k: int(c) for k, c in zip(SLIDE_COUNTS, cnt)}
+    info["max_d2"] = float(mx[0])
+    return info
+
+
+def boundary_faces(F, nP=None):
+    """mmadmm_boundary_faces (host only): the faces of F with no neighbour, nFaces x D vertex ids; ids
+    ascend with (simplex id, local opposite vertex), a face's vertices are its simplex's other vertices
+    in local order."""
+    F = np.ascontiguousarray(F, dtype=np.int32)
+    D = F.shape[1] - 1
+    nP = int(F.max()) + 1 if nP is None else nP
+    n = ctypes.c_int32()
+    _check(lib().mmadmm_boundary_faces(D, nP, F.shape[0], _ip(F), ctypes.byref(n), None))
+    faces = np.zeros((n.value, D), dtype=np.int32)
+    _check(lib().mmadmm_boundary_faces(D, nP, F.shape[0], _ip(F), None, _ip(faces)))
+    return faces
+
+
+def boundary_project(Xp, F, mask, X, anchor=None):
+    """mmadmm_boundary_project_field (host only, no device): the BOUNDARY_FREE nodes of X that lie on a
+    boundary face of F projected onto the boundary surface frozen at Xp -> (X_new, anchor_new, info).
+    anchor: nP node ids (None: every node its own anchor); info holds SLIDE_COUNTS and "max_d2".  F is
+    used as given: pass Engine.simplices() to reproduce Engine.project_boundary bit for bit."""
+    Xp = np.ascontiguousarray(Xp, dtype=np.float64)
+    F = np.ascontiguousarray(F, dtype=np.int32)
+    mask = np.ascontiguousarray(mask, dtype=np.int32)
+    if Xp.ndim != 2 or F.ndim != 2 or F.shape[1] != Xp.shape[1] + 1 or mask.shape != (Xp.shape[0],):
+        raise ValueError("boundary_project: Xp nP x D, F nF x (D + 1), mask nP")
+    nP, D = Xp.shape
+    out = np.array(X, dtype=np.float64, copy=True, order="C")
+    if out.size != nP * D:
+        raise ValueError(f"boundary_project: X must hold {nP * D} values")
+    a = np.arange(nP, dtype=np.int32) if anchor is None else np.array(anchor, dtype=np.int32, copy=True, order="C")
+    if a.shape != (nP,):
+        raise ValueError("boundary_project: anchor must hold nP node ids")
+    cnt = np.zeros(5, dtype=np.int32)
+    mx = np.zeros(1)
+    _check(lib().mmadmm_boundary_project_field(D, nP, _dp(Xp), F.shape[0], _ip(F), _ip(mask), _ip(a), _dp(out),
+                                               _ip(cnt), _dp(mx)))
+    return out, a, _slide_info(cnt, mx)
 
 
 QUALITY_IDENTITY, QUALITY_VALUES, QUALITY_LAST = 0, 1, 2  # MMADMM_QUALITY_*
@@ -1104,6 +1160,57 @@ class Engine:
         if where:
             info["where"] = w
         return out, info
+
+    # -- the sliding boundary (include/mmadmm.h: mmadmm_set_boundary_slide ...)
+    def set_boundary_slide(self, on=True):
+        """BOUNDARY_FREE nodes slide on the boundary: every step() ends by projecting them onto the
+        boundary surface, on the device.  The first call with on=True freezes that surface from the
+        current "points"; on=False stops projecting (the surface and the anchors are kept).
+        euler_step and backwards_euler_step move INTERIOR nodes only and project nothing."""
+        _check(lib().mmadmm_set_boundary_slide(self.h, int(on)))
+
+    def boundary_refreeze(self):
+        """Freeze the boundary surface again from the current "points"; every anchor is reset."""
+        _check(lib().mmadmm_boundary_refreeze(self.h))
+
+    def boundary(self):
+        """-> (faces nFaces x D, sliding node ids, their anchors) of the frozen surface."""
+        nf, ns = ctypes.c_int32(), ctypes.c_int32()
+        _check(lib().mmadmm_boundary_info(self.h, ctypes.byref(nf), ctypes.byref(ns), None, None, None))
+        faces = np.zeros((nf.value, self.dim), dtype=np.int32)
+        ids = np.zeros(ns.value, dtype=np.int32)
+        anchors = np.zeros(ns.value, dtype=np.int32)
+        _check(lib().mmadmm_boundary_info(self.h, None, None, _ip(faces), _ip(ids), _ip(anchors)))
+        return faces, ids, anchors
+
+    def project_boundary(self, X, counts=True):
+        """The sliding nodes of the caller's positions X (nP x D) projected onto the frozen surface with
+        the engine's anchors, which advance (mmadmm_project_boundary) -> (X_new, info).  A numpy array
+        goes through the host call and comes back as a new array; a float64 CUDA tensor is projected in
+        place on torch's current stream (X_new is X).  info holds SLIDE_COUNTS and "max_d2" (reading
+        them waits for the kernel); counts=False: info is None and a tensor call does not wait."""
+        nx = self.nP * self.dim
+        cnt = np.zeros(5, dtype=np.int32)
+        mx = np.zeros(1)
+        pc, pm = (_ip(cnt), _dp(mx)) if counts else (None, None)
+        if _is_tensor(X):
+            px, st, j = self._device_arg(X, nx, "project_boundary")
+            _check(lib().mmadmm_project_boundary_device(self.h, px, st, pc, pm))
+            self._rejoin(j)
+            out = X
+        else:
+            out = np.array(X, dtype=np.float64, copy=True, order="C")
+            if out.size != nx:
+                raise ValueError(f"project_boundary: X must hold {nx} values")
+            _check(lib().mmadmm_project_boundary(self.h, _dp(out), pc, pm))
+        return out, (_slide_info(cnt, mx) if counts else None)
+
+    def slide_counts(self):
+        """SLIDE_COUNTS and "max_d2" of the last step's projection (one small read-back)."""
+        cnt = np.zeros(5, dtype=np.int32)
+        mx = np.zeros(1)
+        _check(lib().mmadmm_slide_counts(self.h, _ip(cnt), _dp(mx)))
+        return _slide_info(cnt, mx)
 
     def quality(self, M=None, X=None, per_simplex=True):
         """Huang's geometry, alignment and equidistribution measures of the mesh (include/mmadmm.h:
