@@ -349,6 +349,56 @@ int mmadmm_boundary_project_field(int dim, int nP, const double* X0, int nF, con
 /* The boundary faces of F as above (host only): *nFaces, and faces (nFaces x dim) when not NULL. */
 int mmadmm_boundary_faces(int dim, int nP, int nF, const int32_t* F, int* nFaces, int32_t* faces);
 
+/* ---- engine state: device snapshot, rollback, checkpoint (no reference counterpart)
+ * One blob, three carriers: the caller's device buffer, the caller's host buffer, a file.  The blob is
+ * a 512-byte little-endian header and a payload of sections in the canonical, simplex-major order of
+ * mmadmm_get (x, xPrev, xBar, points; z, u; hess; the monitor grid's box and values; with a frozen
+ * sliding boundary its surface positions and anchors), so it does not depend on how the library was
+ * built or on the engine's MMX_* switches.  It carries the step counters and flags, a fingerprint of
+ * what the engine was created from (simplices, node ids, mask, dt, tau, rho, grad_use) and a checksum
+ * of the payload.  A run that is saved, destroyed, created again from the same arguments, loaded and
+ * continued takes the steps of the uninterrupted run bit for bit (mmadmm_step; the backward-Euler
+ * Jacobian is not saved and is rebuilt by the first such step after a load).  The monitor callback and
+ * the switches stay the loading engine's own.  Statistics and timers are not saved.
+ *   mmadmm_state_bytes        the size of the blob the engine would save now
+ *   mmadmm_state_save         into cap bytes of host memory
+ *   mmadmm_state_save_device  into cap bytes of device memory (8-byte aligned), written on the engine's
+ *                             stream; consumer_stream (a hipStream_t) is ordered after the writes with an
+ *                             event, NULL: the call returns when they are done.  One host wait (the checksum)
+ *   mmadmm_state_load         from a host blob of exactly `bytes` bytes
+ *   mmadmm_state_load_device  from a device blob; producer_stream is the stream that wrote it (NULL: ready)
+ *   mmadmm_state_write_file / _read_file   the same bytes to / from a file (MMADMM_ERR_IO on failure)
+ * A load validates first and writes afterwards: a refused load leaves the engine bit for bit as it
+ * was.  Refused (MMADMM_ERR_INVALID, the message names the field): a NULL argument, cap too small,
+ * bytes too short or too long, bad magic, a newer version, a section table that does not tile the
+ * payload, another dim / nP / nF / nranks / rank / grid size, another fingerprint, a wrong checksum.
+ * On an element partition every rank saves and loads its own blob, without communication.  A blob
+ * saved with the sliding boundary frozen installs the surface and the anchors and the saved on / off.
+ * Host only, no device: mmadmm_state_info fills *out from a blob's header (bytes = 512: the header
+ * alone; else the whole blob, whose checksum is verified); mmadmm_state_checksum is the payload
+ * checksum, the sum over the 64-bit little-endian words w_i of w_i (2 i + 1) mod 2^64 (bytes: a
+ * multiple of 8, else 0 is returned and the last error set). */
+#define MMADMM_STATE_MAX_SECTIONS 16
+typedef struct mmadmm_state_header {
+  int version, dim, nranks, rank;
+  long long nP, nF, steps_taken, grid_rows, n_sliding;
+  int hess_computed, step_taken, be_step_taken, regrid_each_step, slide_on, slide_frozen;
+  unsigned long long fingerprint, payload_bytes, checksum;
+  int n_sections;
+  char tags[MMADMM_STATE_MAX_SECTIONS][8]; /* zero-padded */
+  long long offsets[MMADMM_STATE_MAX_SECTIONS]; /* from the payload's first byte */
+  long long sizes[MMADMM_STATE_MAX_SECTIONS];
+} mmadmm_state_header;
+int mmadmm_state_bytes(mmadmm_handle h, long long* bytes);
+int mmadmm_state_save(mmadmm_handle h, void* buf, long long cap);
+int mmadmm_state_save_device(mmadmm_handle h, void* d_buf, long long cap, void* consumer_stream);
+int mmadmm_state_load(mmadmm_handle h, const void* buf, long long bytes);
+int mmadmm_state_load_device(mmadmm_handle h, const void* d_buf, long long bytes, void* producer_stream);
+int mmadmm_state_write_file(mmadmm_handle h, const char* path);
+int mmadmm_state_read_file(mmadmm_handle h, const char* path);
+int mmadmm_state_info(const void* buf, long long bytes, mmadmm_state_header* out);
+unsigned long long mmadmm_state_checksum(const void* payload, long long bytes);
+
 const char* mmadmm_last_error(void);
 int mmadmm_version(void);
 /* provenance (no reference counterpart): "src_hash=<16 hex> git=<describe> arch=gfx950", the hash of

@@ -19,6 +19,7 @@
 
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -149,6 +150,39 @@ public:
         mmadmm_cxx::check(onDevice ? mmadmm_project_boundary_device(h_, X, nullptr, nullptr, nullptr)
                                    : mmadmm_project_boundary(h_, X, nullptr, nullptr));
     }
+    // The engine's whole state as one blob (no reference counterpart: the reference's FromFile restart
+    // keeps the points alone; include/mmadmm.h: mmadmm_state_*).  saveState(path) writes a
+    // checkpoint; loadState(path) into an integrator created from the same mesh, monitor, dt, tau and
+    // rho continues the saved run bit for bit (stepsTaken and the Mesh's Vp follow).  The buffer
+    // flavours are the snapshot to roll back to after a failed step: stateBytes() bytes, in host memory
+    // or (onDevice) in device memory, 8-byte aligned and ready; after a device load stepsTaken, this
+    // class's own count, is left to the caller (the header is in device memory).  A blob that does
+    // not fit this integrator is refused (mmadmm_cxx::Error, MMADMM_ERR_INVALID) and changes nothing
+    long long stateBytes() {
+        long long n = 0;
+        mmadmm_cxx::check(mmadmm_state_bytes(h_, &n));
+        return n;
+    }
+    void saveState(const char *path) { mmadmm_cxx::check(mmadmm_state_write_file(h_, path)); }
+    void saveState(void *buf, long long cap, bool onDevice = false) {
+        mmadmm_cxx::check(onDevice ? mmadmm_state_save_device(h_, buf, cap, nullptr) : mmadmm_state_save(h_, buf, cap));
+    }
+    void loadState(const char *path) {
+        mmadmm_cxx::check(mmadmm_state_read_file(h_, path));
+        unsigned char head[512] = {0};
+        if (FILE *f = std::fopen(path, "rb")) {
+            const size_t got = std::fread(head, 1, sizeof head, f);
+            std::fclose(f);
+            afterLoad(got == sizeof head ? head : nullptr);
+        } else {
+            afterLoad(nullptr);
+        }
+    }
+    void loadState(const void *buf, long long bytes, bool onDevice = false) {
+        mmadmm_cxx::check(onDevice ? mmadmm_state_load_device(h_, buf, bytes, nullptr)
+                                   : mmadmm_state_load(h_, buf, bytes));
+        afterLoad(onDevice ? nullptr : buf);
+    }
     // the engine behind this integrator, for the C-ABI calls the reference's class has no name for
     mmadmm_handle handle() const { return h_; }
 
@@ -176,6 +210,14 @@ public:
 
 private:
     mmadmm_handle h_ = nullptr;
+
+    // after a load: the Mesh's Vp, and this class's step count from the blob's header (head: its 512
+    // bytes in host memory; null for a device blob, whose count stays the caller's to set)
+    void afterLoad(const void *head) {
+        mmadmm_state_header hd;
+        if (head && mmadmm_state_info(head, 512, &hd) == MMADMM_OK) stepsTaken = (int)hd.steps_taken;
+        a->updateAfterStep();
+    }
 
     void output(const char *what, const char *fname) {
         int nP = 0, nF = 0, rows = 0;

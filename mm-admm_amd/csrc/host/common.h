@@ -48,6 +48,9 @@ int guarded(Fn&& f) {
 // dst <- src (bytes) on stream st through pinned staging buffers (staging.cpp); src may be freed
 // when it returns
 void upload_staged(void* dst, const void* src, size_t bytes, hipStream_t st);
+// the other way (the state blob's host path): host dst <- device src through the same pinned pairs,
+// one chunk's DMA under the previous chunk's host copy; dst is complete when it returns
+void download_staged(void* dst, const void* src, size_t bytes, hipStream_t st);
 // before a stream that upload_staged has used is destroyed: its uploads are waited for, and the
 // staging events recorded on it are never looked at again
 void staging_forget(hipStream_t st);

@@ -19,11 +19,13 @@
 #include "../kernels/quality_kernels.h"
 #include "../kernels/regrid_kernels.h"
 #include "../kernels/slide_kernels.h"
+#include "../kernels/state_kernels.h"
 #include "../kernels/transfer_kernels.h"
 #include "comm.h"
 #include "common.h"
 #include "partition.h"
 #include "slide.h"
+#include "state.h"
 #include "transfer.h"
 #include "xup_records.h"
 
@@ -88,6 +90,15 @@ struct EngineBase {
   virtual void boundaryInfo(int* nFaces, int* nSliding, int32_t* faces, int32_t* sliding, int32_t* anchors) = 0;
   virtual void projectBoundary(double* X, int* counts, double* maxD2, bool onDevice, void* stream) = 0;
   virtual void slideCounts(int* counts, double* maxD2) = 0;
+  // the state blob (mmadmm_state_*): its size now; to / from a device buffer, a host
+  // buffer, a file
+  virtual long long stateBytes() = 0;
+  virtual void stateSaveDevice(void* dBuf, long long cap, void* stream) = 0;
+  virtual void stateLoadDevice(const void* dBuf, long long bytes, void* stream) = 0;
+  virtual void stateSaveHost(void* buf, long long cap) = 0;
+  virtual void stateLoadHost(const void* buf, long long bytes) = 0;
+  virtual void stateWriteFile(const char* path) = 0;
+  virtual void stateReadFile(const char* path) = 0;
   virtual void debugBlockGrad(int s, const double* z, const double* dx, int flags, double* out) = 0;
   virtual std::string options() const = 0;
 };
@@ -365,6 +376,7 @@ class Engine final : public EngineBase {
     if (evIn_) (void)hipEventDestroy(evIn_);
     if (evOut_) (void)hipEventDestroy(evOut_);
     if (resH_) (void)hipHostFree(resH_);
+    if (stH_) (void)hipHostFree(stH_);
     if (evProx_) (void)hipEventDestroy(evProx_);
     if (evEx_) (void)hipEventDestroy(evEx_);
     for (hipStream_t s : {st2_, st_})
@@ -1319,7 +1331,7 @@ class Engine final : public EngineBase {
     if (source != kQualityIdentity && source != kQualityValues && source != kQualityLast)
       throw Error(MMADMM_ERR_INVALID, who + ": unknown monitor source");
     if (source == kQualityValues && !M) throw Error(MMADMM_ERR_INVALID, who + ": MMADMM_QUALITY_VALUES needs M");
-    if (source == kQualityLast && !rgMon_.p)
+    if (source == kQualityLast && !(rgMon_.p && rgMonValid_))
       throw Error(MMADMM_ERR_INVALID, who + ": MMADMM_QUALITY_LAST before any rebuild of the monitor grid");
     if (!q && !summary) throw Error(MMADMM_ERR_INVALID, who + ": q and summary are both NULL");
     qualityScratch();
@@ -1367,10 +1379,18 @@ class Engine final : public EngineBase {
   // ---- the sliding boundary (slide_kernels.hip)
   // the surface frozen at the current points: faces, the CSR of faces at every node, the sliding
   // nodes and their anchors (each its own node), uploaded once per freeze
-  void slideFreeze() {
+  std::vector<int32_t> localMask() const {
     std::vector<int32_t> maskL(nP_);
     for (int v = 0; v < nP_; ++v) maskL[v] = maskH_[plan_.localNodes[v]];
+    return maskL;
+  }
+  void slideFreeze() {
+    const std::vector<int32_t> maskL = localMask();
     build_slide_surface(D, nP_, nF_, plan_.Flocal.data(), maskL.data(), slS_);
+    slideInstall(maskL);
+  }
+  // the surface slS_ onto the device, frozen at the current points, every sliding node its own anchor
+  void slideInstall(const std::vector<int32_t>& maskL) {
     static const int32_t none[1] = {0};
     auto up = [&](DevBuf<int32_t>& b, const std::vector<int32_t>& h) {
       b.upload(h.empty() ? none : h.data(), std::max<size_t>(h.size(), 1), st_);
@@ -1465,6 +1485,385 @@ class Engine final : public EngineBase {
     int c5[5];
     slide_fold_counts(cnt, c5, maxD2);
     if (counts) std::copy(c5, c5 + 5, counts);
+  }
+
+  // ---- the state blob (state.h, state_kernels.hip)
+  // FNV-1a over: this rank's re-oriented simplices in global node ids, its nodes' global ids, their
+  // mask, the bits of dt, tau, rho, and grad_use (int32) -- in that order
+  uint64_t stateFingerprint() {
+    if (stFpDone_) return stFp_;
+    std::vector<int32_t> Fg(plan_.Flocal.size());
+    getSimplices(Fg.data());
+    const std::vector<int32_t> maskL = localMask();
+    const double p3[3] = {prm_.dt, prm_.tau, prm_.rho};
+    const int32_t gu = prm_.grad_use;
+    uint64_t h = kFnvBasis;
+    h = state_fnv1a(h, Fg.data(), Fg.size() * sizeof(int32_t));
+    h = state_fnv1a(h, plan_.localNodes.data(), plan_.localNodes.size() * sizeof(int32_t));
+    h = state_fnv1a(h, maskL.data(), maskL.size() * sizeof(int32_t));
+    h = state_fnv1a(h, p3, sizeof p3);
+    h = state_fnv1a(h, &gu, sizeof gu);
+    stFp_ = h;
+    stFpDone_ = true;
+    return h;
+  }
+  // the header of the blob this engine writes (a load: would write for a blob with these sliding figures)
+  StateHeader stateDescribe(bool frozen, long long nSliding) {
+    StateHeader h;
+    state_header_init(h);
+    h.dim = D;
+    h.nranks = nranks_;
+    h.rank = rank_;
+    h.nP = nP_;
+    h.nF = nF_;
+    h.stepsTaken = stepsTaken_;
+    h.gridRows = (int64_t)(gvals_.n / (D * D));
+    h.nSliding = frozen ? nSliding : 0;
+    h.flags = (hessComputed_ ? kStHessComputed : 0u) | (stepTaken_ ? kStStepTaken : 0u) |
+              (beStepTaken_ ? kStBeStepTaken : 0u) | (regridEachStep_ ? kStRegridEachStep : 0u) |
+              (slideOn_ ? kStSlideOn : 0u) | (frozen ? kStSlideFrozen : 0u);
+    h.fingerprint = stateFingerprint();
+    const uint64_t nx = (uint64_t)nP_ * D * sizeof(double), nz = (uint64_t)nF_ * K * sizeof(double);
+    state_header_add(h, "x", nx);
+    state_header_add(h, "xPrev", nx);
+    state_header_add(h, "xBar", nx);
+    state_header_add(h, "points", nx);
+    state_header_add(h, "z", nz);
+    state_header_add(h, "u", nz);
+    state_header_add(h, "hess", nz * K);
+    state_header_add(h, "gbox", 6 * sizeof(double));  // the grid's linspace end points lo[3], hi[3]
+    state_header_add(h, "grid", (uint64_t)gvals_.n * sizeof(double));
+    if (frozen) {
+      state_header_add(h, "slX0", nx);
+      state_header_add(h, "slAnchor", ((uint64_t)nSliding * sizeof(int32_t) + 7) & ~(uint64_t)7);
+    }
+    return h;
+  }
+  StateHeader stateDescribeNow() { return stateDescribe(slFrozen_, (long long)slS_.sliding.size()); }
+  long long stateBytes() override { return (long long)(kStateHeaderBytes + stateDescribeNow().payloadBytes); }
+
+  // the checksum slots and the pinned block {header image, grid box, slots' copy}; one chunk of device
+  // memory for the pieces that go through a kernel on the host and file paths (hess; z, u interleaved)
+  static constexpr size_t kStHostBox = kStateHeaderBytes, kStHostSlots = kStateHeaderBytes + 64;
+  void stateScratch() {
+    if (stSlots_.p) return;
+    stSlots_.alloc(kStateSumWords);
+    MMX_HIP(hipHostMalloc((void**)&stH_, kStHostSlots + kStateSumWords * sizeof(unsigned long long), hipHostMallocDefault));
+  }
+  static constexpr size_t kStBlockBytes = (size_t)64 * K * K * sizeof(double);  // a Bkinv block of 64 simplices
+  static bool tagIs(const StateSection& s, const char* t) { return strncmp(s.tag, t, sizeof s.tag) == 0; }
+  // the largest piece of a section the host path moves at once: hess in whole 64-simplex blocks
+  static uint64_t statePiece(const StateSection& s) {
+    return tagIs(s, "hess") ? kStateChunk / kStBlockBytes * kStBlockBytes : (uint64_t)kStateChunk;
+  }
+  bool stateViaKernel(const StateSection& s) const {
+    return tagIs(s, "hess") || (kZUInterleaved && (tagIs(s, "z") || tagIs(s, "u")));
+  }
+  void stateChunk(const StateSection& s) {
+    const size_t need = (size_t)std::min<uint64_t>(statePiece(s), std::max<uint64_t>(s.bytes, 8)) / sizeof(double);
+    if (stChunk_.n < need) stChunk_.alloc(need);
+  }
+  // a plain section's device array (null: hess, interleaved z / u, gbox)
+  void* statePlain(const StateSection& s) {
+    if (tagIs(s, "x")) return x_.p;
+    if (tagIs(s, "xPrev")) return xPrev_.p;
+    if (tagIs(s, "xBar")) return xBar_.p;
+    if (tagIs(s, "points")) return Vp_.p;
+    if (tagIs(s, "grid")) return gvals_.p;
+    if (tagIs(s, "slX0")) return slX0_.p;
+    if (tagIs(s, "slAnchor")) return slAnchor_.p;
+    if (!kZUInterleaved && tagIs(s, "z")) return z_.p;
+    if (!kZUInterleaved && tagIs(s, "u")) return u_.p;
+    return nullptr;
+  }
+  // the bytes of a plain section that exist on the device (slAnchor: the blob pads it to 8 bytes)
+  uint64_t stateLive(const StateSection& s) const {
+    return tagIs(s, "slAnchor") ? (uint64_t)slS_.sliding.size() * sizeof(int32_t) : s.bytes;
+  }
+  // bytes [off, off + n) of a kernel section: device array -> dst (device memory), and back
+  void statePackPiece(const StateSection& s, uint64_t off, uint64_t n, void* dst) {
+    if (tagIs(s, "hess")) {
+      launch_state_pack_b<D>(B_.p, (double*)dst, nF_, (int)(off / kStBlockBytes), (int)((n + kStBlockBytes - 1) / kStBlockBytes), st_);
+    } else {
+      const bool isZ = tagIs(s, "z");
+      launch_state_pack_zu<D>(z_.p, isZ ? (double*)dst : nullptr, isZ ? nullptr : (double*)dst, (long long)(off / 8),
+                              (long long)(n / 8), st_);
+    }
+    MMX_HIP(hipGetLastError());
+  }
+  void stateUnpackPiece(const StateSection& s, uint64_t off, uint64_t n, const void* src) {
+    if (tagIs(s, "hess")) {
+      // the section's last piece also zeroes the padding blocks up to the 256-simplex chunk
+      const int blk0 = (int)(off / kStBlockBytes);
+      const int blkEnd = off + n >= s.bytes ? (nF_ + 255) / 256 * 4 : (int)((off + n) / kStBlockBytes);
+      launch_state_unpack_b<D>((const double*)src, B_.p, nF_, blk0, blkEnd - blk0, st_);
+    } else {
+      const bool isZ = tagIs(s, "z");
+      launch_state_unpack_zu<D>(isZ ? (const double*)src : nullptr, isZ ? nullptr : (const double*)src, z_.p,
+                                (long long)(off / 8), (long long)(n / 8), st_);
+    }
+    MMX_HIP(hipGetLastError());
+  }
+
+  // mmadmm_state_save_device: every section straight into the caller's buffer, the checksum over it
+  // there, one host wait for the slots, then the header
+  void stateSaveDevice(void* dBuf, long long cap, void* stream) override {
+    const StateHeader h0 = stateDescribeNow();
+    StateHeader h = h0;
+    const long long total = (long long)(kStateHeaderBytes + h.payloadBytes);
+    if (cap < total)
+      throw Error(MMADMM_ERR_INVALID, "mmadmm_state_save_device: cap = " + std::to_string(cap) + " is too small (the blob has " +
+                                          std::to_string(total) + " bytes)");
+    if ((uintptr_t)dBuf & 7) throw Error(MMADMM_ERR_INVALID, "mmadmm_state_save_device: d_buf must be 8-byte aligned");
+    stateScratch();
+    char* pay = static_cast<char*>(dBuf) + kStateHeaderBytes;
+    for (uint32_t i = 0; i < h.nSections; ++i) {
+      const StateSection& s = h.sec[i];
+      char* dst = pay + s.offset;
+      if (tagIs(s, "gbox")) {
+        double box[6] = {grid_.lo[0], grid_.lo[1], grid_.lo[2], grid_.hi[0], grid_.hi[1], grid_.hi[2]};
+        std::memcpy(stH_ + kStHostBox, box, sizeof box);
+        MMX_HIP(hipMemcpyAsync(dst, stH_ + kStHostBox, sizeof box, hipMemcpyHostToDevice, st_));
+      } else if (stateViaKernel(s)) {
+        statePackPiece(s, 0, s.bytes, dst);
+      } else {
+        const uint64_t live = stateLive(s);
+        if (live < s.bytes) MMX_HIP(hipMemsetAsync(dst, 0, s.bytes, st_));
+        if (live) MMX_HIP(hipMemcpyAsync(dst, statePlain(s), live, hipMemcpyDeviceToDevice, st_));
+      }
+    }
+    h.checksum = stateDeviceSum(pay, h.payloadBytes);
+    std::memcpy(stH_, &h, sizeof h);
+    MMX_HIP(hipMemcpyAsync(dBuf, stH_, sizeof h, hipMemcpyHostToDevice, st_));
+    beforeConsumer(stream);
+  }
+  // the checksum of a payload in device memory (one host wait)
+  uint64_t stateDeviceSum(const void* pay, uint64_t bytes) {
+    MMX_HIP(hipMemsetAsync(stSlots_.p, 0, kStateSumWords * sizeof(unsigned long long), st_));
+    launch_state_checksum(pay, (long long)(bytes / 8), 0, stSlots_.p, st_);
+    MMX_HIP(hipGetLastError());
+    MMX_HIP(hipMemcpyAsync(stH_ + kStHostSlots, stSlots_.p, kStateSumWords * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                           st_));
+    streamWait();
+    return state_fold_sum(reinterpret_cast<const unsigned long long*>(stH_ + kStHostSlots));
+  }
+
+  // bytes [off, off + n) of section s into host memory, through the pinned staging
+  void stateSectionToHost(const StateSection& s, uint64_t off, uint64_t n, char* dst) {
+    if (tagIs(s, "gbox")) {
+      const double box[6] = {grid_.lo[0], grid_.lo[1], grid_.lo[2], grid_.hi[0], grid_.hi[1], grid_.hi[2]};
+      std::memcpy(dst, box, sizeof box);
+    } else if (stateViaKernel(s)) {
+      stateChunk(s);
+      statePackPiece(s, off, n, stChunk_.p);
+      download_staged(dst, stChunk_.p, n, st_);
+    } else {
+      const uint64_t live = stateLive(s), m = off < live ? std::min(n, live - off) : 0;
+      if (m < n) std::memset(dst + m, 0, n - m);
+      if (m) download_staged(dst, static_cast<const char*>(statePlain(s)) + off, m, st_);
+    }
+  }
+  void stateSectionFromHost(const StateSection& s, uint64_t off, uint64_t n, const char* src) {
+    if (tagIs(s, "gbox")) {
+      std::memcpy(stBox_, src, sizeof stBox_);
+    } else if (stateViaKernel(s)) {
+      stateChunk(s);
+      upload_staged(stChunk_.p, src, n, st_);
+      stateUnpackPiece(s, off, n, stChunk_.p);
+    } else {
+      const uint64_t live = stateLive(s), m = off < live ? std::min(n, live - off) : 0;
+      if (m) upload_staged(static_cast<char*>(statePlain(s)) + off, src, m, st_);
+    }
+  }
+  // the payload, piece by piece in blob order
+  template <class Fn>
+  static void stateForPieces(const StateHeader& h, Fn&& fn) {
+    for (uint32_t i = 0; i < h.nSections; ++i) {
+      const StateSection& s = h.sec[i];
+      const uint64_t piece = statePiece(s);
+      for (uint64_t off = 0; off < s.bytes; off += piece) fn(s, off, std::min(piece, s.bytes - off));
+    }
+  }
+
+  void stateSaveHost(void* buf, long long cap) override {
+    StateHeader h = stateDescribeNow();
+    const long long total = (long long)(kStateHeaderBytes + h.payloadBytes);
+    if (cap < total)
+      throw Error(MMADMM_ERR_INVALID, "mmadmm_state_save: cap = " + std::to_string(cap) + " is too small (the blob has " +
+                                          std::to_string(total) + " bytes)");
+    char* pay = static_cast<char*>(buf) + kStateHeaderBytes;
+    uint64_t sum = 0;
+    stateForPieces(h, [&](const StateSection& s, uint64_t off, uint64_t n) {
+      char* dst = pay + s.offset + off;
+      stateSectionToHost(s, off, n, dst);
+      sum = state_checksum_add(sum, (s.offset + off) / 8, dst, n);
+    });
+    streamWait();
+    h.checksum = sum;
+    std::memcpy(buf, &h, sizeof h);
+  }
+
+  void stateWriteFile(const char* path) override {
+    StateHeader h = stateDescribeNow();
+    StateFile f;
+    auto io = [&](const std::string& msg) {
+      if (!msg.empty()) throw Error(MMADMM_ERR_IO, std::string("mmadmm_state_write_file: ") + msg + " ('" + path + "')");
+    };
+    io(f.open(path, "wb"));
+    io(f.write(&h, sizeof h));  // (rewritten below with the checksum)
+    std::vector<char> tmp;
+    uint64_t sum = 0;
+    stateForPieces(h, [&](const StateSection& s, uint64_t off, uint64_t n) {
+      if (tmp.size() < n) tmp.resize(n);
+      stateSectionToHost(s, off, n, tmp.data());
+      sum = state_checksum_add(sum, (s.offset + off) / 8, tmp.data(), n);
+      io(f.write(tmp.data(), n));
+    });
+    streamWait();
+    h.checksum = sum;
+    io(f.seek(0));
+    io(f.write(&h, sizeof h));
+    io(f.close());
+  }
+
+  // what a load checks before it writes anything: the blob's own structure (state_parse, done by the
+  // caller), then the blob against this engine; the surface a frozen blob needs is built here (host only)
+  void stateValidate(const char* who, const StateHeader& b, SlideSurface& surf, bool& needSurface) {
+    const bool frozen = (b.flags & kStSlideFrozen) != 0;
+    if (frozen && nranks_ > 1)
+      throw Error(MMADMM_ERR_INVALID, std::string(who) + ": state: a frozen sliding boundary on an element partition");
+    long long nSl = (long long)slS_.sliding.size();
+    needSurface = frozen && !slFrozen_;
+    if (needSurface) {  // the sliding nodes depend on this engine's simplices and mask alone
+      const std::vector<int32_t> maskL = localMask();
+      build_slide_surface(D, nP_, nF_, plan_.Flocal.data(), maskL.data(), surf);
+      nSl = (long long)surf.sliding.size();
+    }
+    const std::string msg = state_match(b, stateDescribe(frozen, nSl));
+    if (!msg.empty()) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": " + msg);
+  }
+  // after validation: the surface a frozen blob brings (before its sections are written)
+  void stateBegin(const StateHeader& b, SlideSurface& surf, bool needSurface) {
+    stateScratch();
+    if (needSurface) {
+      slS_ = std::move(surf);
+      slideInstall(localMask());  // (X0 and the anchors are overwritten by the blob's sections)
+    }
+    slFrozen_ = (b.flags & kStSlideFrozen) != 0;
+    if (!slFrozen_) slS_ = SlideSurface{};
+  }
+  // after the sections: counters and flags from the header, everything derived dropped or re-derived
+  void stateFinish(const StateHeader& b) {
+    stepsTaken_ = (int)b.stepsTaken;
+    hessComputed_ = (b.flags & kStHessComputed) != 0;
+    stepTaken_ = (b.flags & kStStepTaken) != 0;
+    regridEachStep_ = (b.flags & kStRegridEachStep) != 0;
+    slideOn_ = (b.flags & kStSlideOn) != 0;
+    slStepValid_ = false;
+    gcacheValid_ = false;
+    MMX_HIP(hipMemsetAsync(tieCount_.p, 0, 3 * sizeof(unsigned), st_));
+    tiePar_ = 0;
+    // the backward-Euler Jacobian is not part of the blob: the next such step builds it as a first step
+    // does (the symbolic factor of an existing matrix depends on the pattern alone and is kept)
+    beStepTaken_ = false;
+    jacVp_ = -1;
+    rgMonValid_ = false;
+    vpVersion_++;
+    grid_geometry(D, nranks_ > 1 ? plan_.nP : nP_, stBox_, stBox_ + 3, grid_);
+    uploadGridCoords();
+    gridOnDevice_ = true;
+    if (D == 3) launch_pad_rows(gvals_.p, (long long)(gvals_.n / 9), gpad_.p, st_);
+    updateIso();
+    m_ = makeView();
+    streamWait();
+    MMX_HIP(hipGetLastError());
+  }
+
+  void stateLoadHost(const void* buf, long long bytes) override {
+    StateHeader b;
+    const std::string msg = state_parse(buf, bytes, false, &b);
+    if (!msg.empty()) throw Error(MMADMM_ERR_INVALID, "mmadmm_state_load: " + msg);
+    SlideSurface surf;
+    bool needSurface = false;
+    stateValidate("mmadmm_state_load", b, surf, needSurface);
+    const char* pay = static_cast<const char*>(buf) + kStateHeaderBytes;
+    if (state_checksum_add(0, 0, pay, (size_t)b.payloadBytes) != b.checksum)
+      throw Error(MMADMM_ERR_INVALID, "mmadmm_state_load: state: wrong checksum (the payload does not match its header)");
+    stateBegin(b, surf, needSurface);
+    stateForPieces(b, [&](const StateSection& s, uint64_t off, uint64_t n) {
+      stateSectionFromHost(s, off, n, pay + s.offset + off);
+    });
+    stateFinish(b);
+  }
+
+  void stateReadFile(const char* path) override {
+    const std::string who = "mmadmm_state_read_file";
+    StateFile f;
+    auto io = [&](const std::string& msg) {
+      if (!msg.empty()) throw Error(MMADMM_ERR_IO, who + ": " + msg + " ('" + path + "')");
+    };
+    io(f.open(path, "rb"));
+    const long long size = f.size();
+    if (size < 0) io("state: cannot size the file");
+    char head[kStateHeaderBytes];
+    if (size >= (long long)kStateHeaderBytes) io(f.read(head, sizeof head));
+    StateHeader b;
+    const std::string msg = state_parse(head, size, false, &b);
+    if (!msg.empty()) throw Error(MMADMM_ERR_INVALID, who + ": " + msg);
+    SlideSurface surf;
+    bool needSurface = false;
+    stateValidate(who.c_str(), b, surf, needSurface);
+    std::vector<char> tmp;
+    uint64_t sum = 0;  // first pass: the checksum alone, nothing is written
+    stateForPieces(b, [&](const StateSection& s, uint64_t off, uint64_t n) {
+      if (tmp.size() < n) tmp.resize(n);
+      io(f.read(tmp.data(), n));
+      sum = state_checksum_add(sum, (s.offset + off) / 8, tmp.data(), n);
+    });
+    if (sum != b.checksum)
+      throw Error(MMADMM_ERR_INVALID, who + ": state: wrong checksum (the payload does not match its header)");
+    io(f.seek((long long)kStateHeaderBytes));
+    stateBegin(b, surf, needSurface);
+    stateForPieces(b, [&](const StateSection& s, uint64_t off, uint64_t n) {
+      io(f.read(tmp.data(), n));
+      stateSectionFromHost(s, off, n, tmp.data());
+    });
+    stateFinish(b);
+  }
+
+  void stateLoadDevice(const void* dBuf, long long bytes, void* stream) override {
+    const std::string who = "mmadmm_state_load_device";
+    if (bytes < (long long)kStateHeaderBytes)
+      throw Error(MMADMM_ERR_INVALID, who + ": " + state_parse("", bytes, false, nullptr));
+    if ((uintptr_t)dBuf & 7) throw Error(MMADMM_ERR_INVALID, who + ": d_buf must be 8-byte aligned");
+    stateScratch();
+    afterProducer(stream);
+    MMX_HIP(hipMemcpyAsync(stH_, dBuf, kStateHeaderBytes, hipMemcpyDeviceToHost, st_));
+    streamWait();
+    StateHeader b;
+    const std::string msg = state_parse(stH_, bytes, false, &b);
+    if (!msg.empty()) throw Error(MMADMM_ERR_INVALID, who + ": " + msg);
+    SlideSurface surf;
+    bool needSurface = false;
+    stateValidate(who.c_str(), b, surf, needSurface);
+    const char* pay = static_cast<const char*>(dBuf) + kStateHeaderBytes;
+    if (stateDeviceSum(pay, b.payloadBytes) != b.checksum)
+      throw Error(MMADMM_ERR_INVALID, who + ": state: wrong checksum (the payload does not match its header)");
+    stateBegin(b, surf, needSurface);
+    for (uint32_t i = 0; i < b.nSections; ++i) {
+      const StateSection& s = b.sec[i];
+      const char* src = pay + s.offset;
+      if (tagIs(s, "gbox")) {
+        MMX_HIP(hipMemcpyAsync(stH_ + kStHostBox, src, sizeof stBox_, hipMemcpyDeviceToHost, st_));
+        streamWait();
+        std::memcpy(stBox_, stH_ + kStHostBox, sizeof stBox_);
+      } else if (stateViaKernel(s)) {
+        stateUnpackPiece(s, 0, s.bytes, src);
+      } else if (const uint64_t live = stateLive(s)) {
+        MMX_HIP(hipMemcpyAsync(statePlain(s), src, live, hipMemcpyDeviceToDevice, st_));
+      }
+    }
+    stateFinish(b);  // (ends with a host wait: the caller's buffer has been read)
   }
 
   // mmadmm_get_device: "x" or "points" into the caller's device array
@@ -1935,6 +2334,7 @@ class Engine final : public EngineBase {
     st_stats_.regrid_cand = part ? nG : 0;
     MMX_HIP(hipGetLastError());
     gridOnDevice_ = true;
+    rgMonValid_ = true;
     updateIso();
     m_ = makeView();
     st_stats_.regrids += 1;
@@ -2089,6 +2489,7 @@ class Engine final : public EngineBase {
   void* monUser_ = nullptr;
   bool regridEachStep_ = false, gridOnDevice_ = false;
   DevBuf<double> rgPart_, rgMon_, rgTmp_, rgTmp2_, rgXg_, rgSend_, rgRecv_;
+  bool rgMonValid_ = false;  // rgMon_ holds the monitor of a rebuild since creation or the last state load
   // the monitor from the caller's arrays (regridFrom): the element buffer and nodal gradient of the
   // recovery, staged host input / output, the source of the rebuild in flight, the caller-stream events
   DevBuf<double> fldE_, fldG_, fldIn_, fldOut_;
@@ -2113,6 +2514,14 @@ class Engine final : public EngineBase {
   SlideSurface slS_;
   DevBuf<double> slX0_, slStage_;
   DevBuf<int32_t> slFaces_, slStarPtr_, slStarFace_, slMask_, slIds_, slAnchor_, slCnt_, slStepCnt_;
+  // the state blob: the fingerprint (computed once), the checksum slots, the pinned block of
+  // stateScratch, the one device chunk of the host and file paths, the grid box of the load in flight
+  uint64_t stFp_ = 0;
+  bool stFpDone_ = false;
+  DevBuf<unsigned long long> stSlots_;
+  char* stH_ = nullptr;
+  DevBuf<double> stChunk_;
+  double stBox_[6] = {0, 0, 0, 0, 0, 0};
   double* qlRecH_ = nullptr;
   const double* srcPtr_ = nullptr;
   double srcAlpha_ = 1.0;
@@ -2557,6 +2966,48 @@ int mmadmm_get_device(mmadmm_handle h, const char* what, double* d_out, void* co
   return guarded([&] {
     if (!what || !d_out) throw Error(MMADMM_ERR_INVALID, "mmadmm_get_device: NULL argument");
     eng(h).getDevice(what, d_out, consumer_stream);
+  });
+}
+int mmadmm_state_bytes(mmadmm_handle h, long long* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error(MMADMM_ERR_INVALID, "mmadmm_state_bytes: bytes is NULL");
+    *bytes = eng(h).stateBytes();
+  });
+}
+int mmadmm_state_save(mmadmm_handle h, void* buf, long long cap) {
+  return guarded([&] {
+    if (!buf) throw Error(MMADMM_ERR_INVALID, "mmadmm_state_save: buf is NULL");
+    eng(h).stateSaveHost(buf, cap);
+  });
+}
+int mmadmm_state_save_device(mmadmm_handle h, void* d_buf, long long cap, void* consumer_stream) {
+  return guarded([&] {
+    if (!d_buf) throw Error(MMADMM_ERR_INVALID, "mmadmm_state_save_device: d_buf is NULL");
+    eng(h).stateSaveDevice(d_buf, cap, consumer_stream);
+  });
+}
+int mmadmm_state_load(mmadmm_handle h, const void* buf, long long bytes) {
+  return guarded([&] {
+    if (!buf) throw Error(MMADMM_ERR_INVALID, "mmadmm_state_load: buf is NULL");
+    eng(h).stateLoadHost(buf, bytes);
+  });
+}
+int mmadmm_state_load_device(mmadmm_handle h, const void* d_buf, long long bytes, void* producer_stream) {
+  return guarded([&] {
+    if (!d_buf) throw Error(MMADMM_ERR_INVALID, "mmadmm_state_load_device: d_buf is NULL");
+    eng(h).stateLoadDevice(d_buf, bytes, producer_stream);
+  });
+}
+int mmadmm_state_write_file(mmadmm_handle h, const char* path) {
+  return guarded([&] {
+    if (!path) throw Error(MMADMM_ERR_INVALID, "mmadmm_state_write_file: path is NULL");
+    eng(h).stateWriteFile(path);
+  });
+}
+int mmadmm_state_read_file(mmadmm_handle h, const char* path) {
+  return guarded([&] {
+    if (!path) throw Error(MMADMM_ERR_INVALID, "mmadmm_state_read_file: path is NULL");
+    eng(h).stateReadFile(path);
   });
 }
 int mmadmm_sync(mmadmm_handle h) {

@@ -15,6 +15,7 @@ extern "C" unsigned mmx_layout_admm_euler(void);
 extern "C" unsigned mmx_layout_admm_util(void);
 extern "C" unsigned mmx_layout_sparse(void);
 extern "C" unsigned mmx_layout_chain(void);
+extern "C" unsigned mmx_layout_state(void);
 
 namespace mmx {
 
@@ -28,7 +29,8 @@ void check_kernel_layout(unsigned hostWord) {
               {"admm_kernels_euler", mmx_layout_admm_euler()},
               {"admm_kernels_util", mmx_layout_admm_util()},
               {"sparse_kernels", mmx_layout_sparse()},
-              {"chain_sweep", mmx_layout_chain()}};
+              {"chain_sweep", mmx_layout_chain()},
+              {"state_kernels", mmx_layout_state()}};
   for (const auto& o : objs)
     if (o.word != hostWord) {
       char buf[256];

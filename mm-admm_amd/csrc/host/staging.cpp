@@ -116,4 +116,38 @@ void upload_staged(void* dst, const void* src, size_t bytes, hipStream_t st) {
   // the source may be freed once this returns; the staging chunks are guarded by their events
 }
 
+void download_staged(void* dst, const void* src, size_t bytes, hipStream_t st) {
+  constexpr size_t kChunk = Staging::kChunk;
+  Staging* sg = acquire(st);
+  struct Back {
+    Staging* s;
+    ~Back() { give_back(s); }
+  } back{sg};
+  const char* s = static_cast<const char*>(src);
+  char* d = static_cast<char*>(dst);
+  auto issue = [&](size_t off, int k) {
+    if (sg->pending[k]) MMX_HIP(hipEventSynchronize(sg->ev[k]));  // (an upload's DMA still reading the chunk)
+    MMX_HIP(hipMemcpyAsync(sg->buf[k], s + off, std::min(kChunk, bytes - off), hipMemcpyDeviceToHost, st));
+    MMX_HIP(hipEventRecord(sg->ev[k], st));
+    sg->pending[k] = true;
+  };
+  if (bytes) issue(0, 0);
+  int k = 0;
+  for (size_t off = 0; off < bytes; off += kChunk, k ^= 1) {
+    if (off + kChunk < bytes) issue(off + kChunk, k ^ 1);  // the next chunk's DMA runs under this one's copy
+    MMX_HIP(hipEventSynchronize(sg->ev[k]));
+    sg->pending[k] = false;
+    const size_t n = std::min(kChunk, bytes - off);
+    constexpr size_t kPiece = (size_t)1 << 20;
+    const long long pieces = (long long)((n + kPiece - 1) / kPiece);
+    const char* b = sg->buf[k];
+#pragma omp parallel for schedule(static)
+    for (long long q = 0; q < pieces; ++q) {
+      const size_t o = (size_t)q * kPiece;
+      std::memcpy(d + off + o, b + o, std::min(kPiece, n - o));
+    }
+  }
+  // every chunk has been waited for: dst is complete and the pair has nothing pending
+}
+
 }  // namespace mmx

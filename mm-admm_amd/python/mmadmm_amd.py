@@ -60,6 +60,23 @@ class mmadmm_stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+STATE_HEADER_BYTES = 512
+STATE_MAX_SECTIONS = 16
+
+
+class mmadmm_state_header(ctypes.Structure):
+    _fields_ = [("version", ctypes.c_int), ("dim", ctypes.c_int), ("nranks", ctypes.c_int), ("rank", ctypes.c_int),
+                ("nP", ctypes.c_longlong), ("nF", ctypes.c_longlong), ("steps_taken", ctypes.c_longlong),
+                ("grid_rows", ctypes.c_longlong), ("n_sliding", ctypes.c_longlong),
+                ("hess_computed", ctypes.c_int), ("step_taken", ctypes.c_int), ("be_step_taken", ctypes.c_int),
+                ("regrid_each_step", ctypes.c_int), ("slide_on", ctypes.c_int), ("slide_frozen", ctypes.c_int),
+                ("fingerprint", ctypes.c_ulonglong), ("payload_bytes", ctypes.c_ulonglong),
+                ("checksum", ctypes.c_ulonglong), ("n_sections", ctypes.c_int),
+                ("tags", (ctypes.c_char * 8) * STATE_MAX_SECTIONS),
+                ("offsets", ctypes.c_longlong * STATE_MAX_SECTIONS),
+                ("sizes", ctypes.c_longlong * STATE_MAX_SECTIONS)]
+
+
 class MMADMMError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"mmadmm error {code}: {msg}")
@@ -206,6 +223,16 @@ def lib():
     L.mmadmm_plan_sizes.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int)] * 7
     L.mmadmm_plan_get.argtypes = [vp] + [c_int_p] * 6
     L.mmadmm_plan_destroy.argtypes = [vp]
+    L.mmadmm_state_bytes.argtypes = [vp, c_ll_p]
+    L.mmadmm_state_save.argtypes = [vp, vp, ctypes.c_longlong]
+    L.mmadmm_state_save_device.argtypes = [vp, vp, ctypes.c_longlong, vp]
+    L.mmadmm_state_load.argtypes = [vp, vp, ctypes.c_longlong]
+    L.mmadmm_state_load_device.argtypes = [vp, vp, ctypes.c_longlong, vp]
+    L.mmadmm_state_write_file.argtypes = [vp, ctypes.c_char_p]
+    L.mmadmm_state_read_file.argtypes = [vp, ctypes.c_char_p]
+    L.mmadmm_state_info.argtypes = [vp, ctypes.c_longlong, ctypes.POINTER(mmadmm_state_header)]
+    L.mmadmm_state_checksum.argtypes = [vp, ctypes.c_longlong]
+    L.mmadmm_state_checksum.restype = ctypes.c_ulonglong
     _lib = L
     return L
 
@@ -215,6 +242,38 @@ def build_info():
     buf = ctypes.create_string_buffer(256)
     _check(lib().mmadmm_build_info(buf, 256))
     return dict(kv.split("=", 1) for kv in buf.value.decode().split())
+
+
+def state_checksum(payload):
+    """The state blob's payload checksum (mmadmm_state_checksum): the sum over the 64-bit little-endian
+    words w_i of w_i (2 i + 1) mod 2^64.  Host only."""
+    a = np.frombuffer(bytes(payload), dtype=np.uint8) if not isinstance(payload, np.ndarray) else \
+        np.ascontiguousarray(payload).view(np.uint8).ravel()
+    if a.size % 8:
+        raise ValueError("state_checksum: the payload must be a multiple of 8 bytes")
+    return int(lib().mmadmm_state_checksum(a.ctypes.data_as(ctypes.c_void_p) if a.size else None, a.size))
+
+
+def state_info(blob_or_path):
+    """The header of a state blob as a dict (mmadmm_state_info; host only, no GPU): the counters and
+    flags, sizes, fingerprint, checksum and "sections" {tag: (offset, bytes)}.  A numpy uint8 array or
+    bytes: the whole blob (its checksum is verified) or its first 512 bytes alone; a CUDA tensor is
+    copied to the host; a path: the file's header alone is read."""
+    if isinstance(blob_or_path, (str, os.PathLike)):
+        with open(blob_or_path, "rb") as f:
+            blob_or_path = f.read(STATE_HEADER_BYTES)
+    if _is_tensor(blob_or_path):
+        blob_or_path = blob_or_path.cpu().numpy()
+    if isinstance(blob_or_path, (bytes, bytearray, memoryview)):
+        blob_or_path = np.frombuffer(bytes(blob_or_path), dtype=np.uint8)
+    a = np.ascontiguousarray(blob_or_path, dtype=np.uint8).ravel()
+    h = mmadmm_state_header()
+    _check(lib().mmadmm_state_info(a.ctypes.data_as(ctypes.c_void_p) if a.size else None, a.size, ctypes.byref(h)))
+    d = {k: getattr(h, k) for k, _ in h._fields_ if k not in ("tags", "offsets", "sizes")}
+    for k in ("hess_computed", "step_taken", "be_step_taken", "regrid_each_step", "slide_on", "slide_frozen"):
+        d[k] = bool(d[k])
+    d["sections"] = {bytes(h.tags[i]).rstrip(b"\0").decode(): (h.offsets[i], h.sizes[i]) for i in range(h.n_sections)}
+    return d
 
 
 def _close_at_exit(obj):
@@ -1275,6 +1334,77 @@ class Engine:
         _check(lib().mmadmm_get_device(self.h, what.encode(), p, st))
         self._rejoin(j)
         return out
+
+    # -- the state blob (include/mmadmm.h: mmadmm_state_*)
+    def state_bytes(self):
+        """Bytes of the blob save_state() would write now."""
+        n = ctypes.c_longlong()
+        _check(lib().mmadmm_state_bytes(self.h, ctypes.byref(n)))
+        return n.value
+
+    def _state_tensor_arg(self, t, who):
+        import torch
+
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{who}: a torch tensor must be uint8, contiguous, on the GPU "
+                             f"(got {t.dtype}, {t.device})")
+        if self.device is not None and self.device >= 0 and t.device.index != self.device:
+            raise ValueError(f"{who}: tensor on {t.device}, the engine on device {self.device}")
+        cur = torch.cuda.current_stream(t.device)
+        if cur.cuda_stream != 0:
+            return t.data_ptr(), cur.cuda_stream, None
+        if self._side is None:
+            self._side = torch.cuda.Stream(t.device)
+        self._side.wait_stream(cur)
+        t.record_stream(self._side)
+        return t.data_ptr(), self._side.cuda_stream, (cur, self._side)
+
+    def save_state(self, out=None, device=False):
+        """The engine's state as one blob: a numpy uint8 array, or (device=True, or `out` a tensor) a
+        uint8 CUDA tensor written on the device and ordered before torch's current stream -- the
+        snapshot to roll back to with load_state.  `out`, when given, must hold state_bytes() bytes; the
+        blob is its first state_bytes() bytes and that view is returned."""
+        n = self.state_bytes()
+        if device or _is_tensor(out):
+            import torch
+
+            if out is None:
+                dev = torch.device("cuda", self.device if self.device is not None and self.device >= 0
+                                   else torch.cuda.current_device())
+                out = torch.empty(n, dtype=torch.uint8, device=dev)
+            p, st, j = self._state_tensor_arg(out, "save_state")
+            _check(lib().mmadmm_state_save_device(self.h, p, out.numel(), st))
+            self._rejoin(j)
+            return out[:n]
+        if out is None:
+            out = np.empty(n, dtype=np.uint8)
+        if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.ndim == 1):
+            raise ValueError("save_state: out must be a contiguous 1-D numpy uint8 array or a uint8 CUDA tensor")
+        _check(lib().mmadmm_state_save(self.h, out.ctypes.data_as(ctypes.c_void_p), out.size))
+        return out[:n]
+
+    def load_state(self, blob):
+        """Put back a blob of save_state / save: a numpy uint8 array, bytes, or a uint8 CUDA tensor.
+        Validated before anything is written: a refused blob (MMADMMError) leaves the engine as it was."""
+        if _is_tensor(blob):
+            p, st, j = self._state_tensor_arg(blob, "load_state")
+            try:
+                _check(lib().mmadmm_state_load_device(self.h, p, blob.numel(), st))
+            finally:
+                self._rejoin(j)
+            return
+        if isinstance(blob, (bytes, bytearray, memoryview)):
+            blob = np.frombuffer(blob, dtype=np.uint8)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        _check(lib().mmadmm_state_load(self.h, blob.ctypes.data_as(ctypes.c_void_p), blob.size))
+
+    def save(self, path):
+        """The blob of save_state() into a file (a checkpoint)."""
+        _check(lib().mmadmm_state_write_file(self.h, os.fsencode(path)))
+
+    def load(self, path):
+        """load_state of a file written by save()."""
+        _check(lib().mmadmm_state_read_file(self.h, os.fsencode(path)))
 
     def block_grad(self, sid, z, dxpu=None, computeGrad=True, regularize=False):
         """Device Mesh::computeBlockGrad of one simplex -> (energy, grad, Igt)."""
