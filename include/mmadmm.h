@@ -254,6 +254,59 @@ int mmadmm_transfer_field(int dim, int nP, const double* Xold, int nF, const int
  * the face of s opposite its local vertex j, or -1. */
 int mmadmm_face_neighbours(int dim, int nP, int nF, const int32_t* F, int32_t* nbr);
 
+/* ---- nodal fields at arbitrary points (no reference counterpart)
+ * mmadmm_transfer finds its target by starting in the node's own patch; these calls need no start
+ * simplex.  mmadmm_locator_build makes, on the device, a uniform-cell locator over the simplices of
+ * mmadmm_get_simplices at the node positions X (nP x D; NULL: the engine's current "points"), of which
+ * the locator keeps its own copy: later steps do not invalidate it, and mmadmm_state_save / _load
+ * neither store nor touch it (derived data; rebuild it after a load if it should follow the loaded
+ * points).
+ *   box     lo / hi: the min / max of X per axis; refused unless finite and hi - lo > 0
+ *   cells   cells[3] per axis (cells[2] = 1 in 2D), or NULL: mmadmm_locator_default_cells, the largest g
+ *           per axis with g^D <= max(1, nF / fill) and g^D <= 2^27, fill = 2 (2D) / 3 (3D).  The cell of
+ *           x on axis k is clamp((int)((x - lo_k) n_k / (hi_k - lo_k)), 0, n_k - 1)
+ *   lists   a simplex is listed in every cell its bounding box, widened by 1e-9 of the box, touches
+ * mmadmm_sample evaluates the piecewise-linear field u (nP x C row-major, C >= 1) at the nQ points Q
+ * (nQ x D) into out (nQ x C).  A point with a component that is not finite, or whose (clamped) cell
+ * lists no simplex, is "none": every component the quiet NaN 0x7ff8000000000000.  Otherwise, over the
+ * simplices its cell lists: the lowest id among those that contain it to -1e-12 in every barycentric
+ * coordinate (mmadmm_transfer's test) is used ("inside"); if none does, the one with the largest
+ * minimum coordinate, the lowest id on ties, and the point is extrapolated linearly ("outside").  A
+ * point outside the box is clamped into the boundary cells first.  where (nQ, may be NULL): -1 none,
+ * s >= 0 inside simplex s, -2 - s outside.  counts (3 host ints, may be NULL): {inside, outside, none};
+ * asking for it costs one small read-back.  The result of a query depends on that query alone and
+ * not on the order of the lists: bitwise reproducible, and the same for every choice of cells as long
+ * as the point is inside the mesh.
+ * The build synchronises the host (three small read-backs) and allocates; a later build reuses the
+ * buffers when it fits.  The _device forms take device arrays (2D: positions and points 16-byte
+ * aligned) ordered after `stream`'s work; mmadmm_sample_device hands the results back to that stream
+ * with no host synchronisation (unless counts is asked for) and allocates nothing; stream NULL: the
+ * data are ready, and the call returns when the results are.  mmadmm_locator_build_device returns
+ * when the locator is complete.  mmadmm_locator_info: cells[3], box[2 dim] = lo then hi, the number of
+ * (cell, simplex) pairs and the longest list; every pointer may be NULL.  mmadmm_locator_free releases
+ * the locator's device memory (mmadmm_destroy does so too).  nQ == 0 succeeds and writes nothing.
+ * Refused (MMADMM_ERR_INVALID): C < 1, nQ < 0, a NULL required array, a cells entry < 1, cells[2] != 1 in
+ * 2D, more than 2^27 cells, a box that is not finite or degenerate, more than INT32_MAX pairs, info or
+ * sample before a build (or after a build that failed), an element partition (single rank only).
+ * Cost to know of: a simplex that spans many cells (a strongly graded mesh) is listed by one lane,
+ * cell after cell.  Zero- or negative-volume simplices are NOT checked. */
+int mmadmm_locator_default_cells(int dim, int nF, int cells[3]);
+int mmadmm_locator_build(mmadmm_handle h, const double* X, const int* cells);
+int mmadmm_locator_build_device(mmadmm_handle h, const double* d_X, const int* cells, void* stream);
+int mmadmm_locator_info(mmadmm_handle h, int cells[3], double* box, long long* pairs, int* max_per_cell);
+int mmadmm_locator_free(mmadmm_handle h);
+int mmadmm_sample(mmadmm_handle h, int nQ, const double* Q, int C, const double* u, double* out, int32_t* where,
+                  int* counts);
+int mmadmm_sample_device(mmadmm_handle h, int nQ, const double* d_Q, int C, const double* d_u, double* d_out,
+                         int32_t* d_where, int* counts, void* stream);
+/* Host only, no device needed: the same result on the CPU in the kernels' arithmetic (bit-identical to
+ * the calls above with F = mmadmm_get_simplices' simplices: F is used as given, not re-oriented), and
+ * what mmadmm_locator_info reports for the same positions, simplices and cells. */
+int mmadmm_sample_field(int dim, int nP, const double* X, int nF, const int32_t* F, const int* cells, int nQ,
+                        const double* Q, int C, const double* u, double* out, int32_t* where, int* counts);
+int mmadmm_locator_field_info(int dim, int nP, const double* X, int nF, const int32_t* F, const int* cells,
+                              int cells_used[3], double* box, long long* pairs, int* max_per_cell);
+
 /* ---- mesh quality against a monitor (no reference counterpart)
  * Huang's three element-wise measures of the engine's mesh, computed on the device.  For simplex K
  * of mmadmm_get_simplices at the positions X (nP x D; NULL: the engine's current "points"): E its

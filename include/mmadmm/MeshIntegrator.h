@@ -128,6 +128,19 @@ public:
         mmadmm_cxx::check(onDevice ? mmadmm_transfer_device(h_, Xold, nullptr, C, uold, unew, nullptr, nullptr, nullptr)
                                    : mmadmm_transfer(h_, Xold, nullptr, C, uold, unew, nullptr, nullptr));
     }
+    // Nodal fields at arbitrary points (no reference counterpart; include/mmadmm.h: mmadmm_locator_build
+    // and mmadmm_sample).  buildLocator: the cell locator over the simplices at the node positions X
+    // (nP x D row-major; nullptr: the current points), automatic cells; it keeps its own copy of X.
+    // sampleField: u (nP x C row-major) evaluated piecewise linearly at the nQ points Q (nQ x D) into
+    // out (nQ x C); a point no cell locates is NaN.  onDevice: the arrays are in device memory and ready
+    void buildLocator(const double *X = nullptr, bool onDevice = false) {
+        mmadmm_cxx::check(onDevice ? mmadmm_locator_build_device(h_, X, nullptr, nullptr)
+                                   : mmadmm_locator_build(h_, X, nullptr));
+    }
+    void sampleField(int nQ, const double *Q, int C, const double *u, double *out, bool onDevice = false) {
+        mmadmm_cxx::check(onDevice ? mmadmm_sample_device(h_, nQ, Q, C, u, out, nullptr, nullptr, nullptr)
+                                   : mmadmm_sample(h_, nQ, Q, C, u, out, nullptr, nullptr));
+    }
     // Huang's geometry, alignment and equidistribution measures of the current mesh (X null) or of the
     // candidate positions X (nP x D row-major) against the monitor `source`: MMADMM_QUALITY_IDENTITY,
     // _VALUES (M: nP x D*D nodal tensors) or _LAST (the nodal monitor of the last grid rebuild, e.g. of

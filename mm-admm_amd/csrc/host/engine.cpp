@@ -16,6 +16,7 @@
 #include "../../../include/mmx_sparse.h"
 #include "../kernels/admm_kernels.h"
 #include "../kernels/field_kernels.h"
+#include "../kernels/locate_kernels.h"
 #include "../kernels/quality_kernels.h"
 #include "../kernels/regrid_kernels.h"
 #include "../kernels/slide_kernels.h"
@@ -23,6 +24,7 @@
 #include "../kernels/transfer_kernels.h"
 #include "comm.h"
 #include "common.h"
+#include "locate.h"
 #include "partition.h"
 #include "slide.h"
 #include "state.h"
@@ -84,6 +86,13 @@ struct EngineBase {
   // mmadmm_quality(_device): Huang's measures of the mesh at X (null: Vp) against the monitor `source`
   virtual void quality(const double* X, int source, const double* M, double* q, double* summary, bool onDevice,
                        void* stream) = 0;
+  // mmadmm_locator_* / mmadmm_sample(_device): the cell locator over the simplices at X (null: Vp) and a
+  // nodal field evaluated at nQ arbitrary points
+  virtual void locatorBuild(const double* X, const int* cells, bool onDevice, void* stream) = 0;
+  virtual void locatorInfo(int* cells, double* box, long long* pairs, int* maxPerCell) = 0;
+  virtual void locatorFree() = 0;
+  virtual void sample(int nQ, const double* Q, int C, const double* u, double* out, int32_t* where, int* counts,
+                      bool onDevice, void* stream) = 0;
   // the sliding boundary (mmadmm_set_boundary_slide ... mmadmm_slide_counts)
   virtual void setBoundarySlide(int on) = 0;
   virtual void boundaryRefreeze() = 0;
@@ -1376,6 +1385,139 @@ class Engine final : public EngineBase {
     if (summary) std::memcpy(summary, qlRecH_, 8 * sizeof(double));
   }
 
+  // ---- the point locator and the field at arbitrary points (locate_kernels.hip)
+  // mmadmm_locator_build / _device: the locator's own copy of the positions, their box (one
+  // read-back), the pair count (one read-back, and the refusal beyond INT32_MAX before any list is
+  // made), count, scan, fill, the longest list (one read-back).  The buffers only grow: a later build
+  // that fits reuses them.  A build that fails leaves no locator.
+  void locatorBuild(const double* X, const int* cells, bool onDevice, void* stream) override {
+    const char* who = onDevice ? "mmadmm_locator_build_device" : "mmadmm_locator_build";
+    singleRankOnly(who);
+    LocateGrid g;
+    locate_set_cells(who, D, nF_, cells, g);
+    locBuilt_ = false;
+    const size_t nx = (size_t)nP_ * D;
+    if (locX_.n < nx) locX_.alloc(nx);
+    if (!locPart_.p) {
+      locPart_.alloc((size_t)256 * 2 * D);
+      locScal_.alloc(2);
+      locCnt_.alloc(kSampleCountInts);
+    }
+    if (!X) {
+      MMX_HIP(hipMemcpyAsync(locX_.p, Vp_.p, nx * sizeof(double), hipMemcpyDeviceToDevice, st_));
+    } else if (!onDevice) {
+      MMX_HIP(hipMemcpyAsync(locX_.p, X, nx * sizeof(double), hipMemcpyHostToDevice, st_));
+    } else {
+      afterProducer(stream);
+      MMX_HIP(hipMemcpyAsync(locX_.p, X, nx * sizeof(double), hipMemcpyDeviceToDevice, st_));
+    }
+    const int nbl = std::max(1, std::min(256, (nP_ + 255) / 256));
+    launch_bbox<D>(locX_.p, nP_, locPart_.p, nbl, st_);
+    MMX_HIP(hipGetLastError());
+    std::vector<double> part((size_t)nbl * 2 * D);
+    MMX_HIP(hipMemcpyAsync(part.data(), locPart_.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, st_));
+    streamWait();  // (the caller's X has been copied: a device array is the caller's again from here)
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int b = 0; b < nbl; ++b)
+      for (int d = 0; d < D; ++d) {
+        const double a = part[(size_t)b * 2 * D + d], c = part[(size_t)b * 2 * D + D + d];
+        lo[d] = a < lo[d] ? a : lo[d];
+        hi[d] = c > hi[d] ? c : hi[d];
+      }
+    locate_set_box(who, D, lo, hi, g);
+    unsigned long long total = 0;
+    launch_locate_volume<D>(locX_.p, F_.p, nF_, g, locScal_.p, st_);
+    MMX_HIP(hipGetLastError());
+    MMX_HIP(hipMemcpyAsync(&total, locScal_.p, sizeof total, hipMemcpyDeviceToHost, st_));
+    streamWait();
+    if (total > (unsigned long long)std::numeric_limits<int32_t>::max())
+      throw Error(MMADMM_ERR_INVALID, std::string(who) + ": more than INT32_MAX (cell, simplex) pairs");
+    const size_t ncell = (size_t)g.n[0] * g.n[1] * g.n[2];
+    const size_t tmpBytes = locate_tmp_bytes((int)ncell);
+    if (locTmp_.n < tmpBytes) locTmp_.alloc(tmpBytes);
+    if (locCounts_.n < ncell + 1) {
+      locCounts_.alloc(ncell + 1);
+      locStarts_.alloc(ncell + 1);
+    }
+    if (locPairs_.n < std::max<size_t>((size_t)total, 1)) locPairs_.alloc(std::max<size_t>((size_t)total, 1));
+    int* dMax = reinterpret_cast<int*>(locScal_.p + 1);
+    launch_locate_count<D>(locX_.p, F_.p, nF_, g, locCounts_.p, locStarts_.p, dMax, locTmp_.p, locTmp_.n, st_);
+    // (the counts have been scanned: their buffer serves as the fill pass's cursors)
+    launch_locate_fill<D>(locX_.p, F_.p, nF_, g, locStarts_.p, locCounts_.p, locPairs_.p, st_);
+    MMX_HIP(hipGetLastError());
+    int mx = 0;
+    MMX_HIP(hipMemcpyAsync(&mx, dMax, sizeof mx, hipMemcpyDeviceToHost, st_));
+    streamWait();
+    locG_ = g;
+    locPairsN_ = (long long)total;
+    locMax_ = mx;
+    locBuilt_ = true;
+  }
+  void locatorInfo(int* cells, double* box, long long* pairs, int* maxPerCell) override {
+    if (!locBuilt_) throw Error(MMADMM_ERR_INVALID, "mmadmm_locator_info: no locator is built");
+    if (cells)
+      for (int k = 0; k < 3; ++k) cells[k] = locG_.n[k];
+    if (box)
+      for (int k = 0; k < D; ++k) {
+        box[k] = locG_.lo[k];
+        box[D + k] = locG_.hi[k];
+      }
+    if (pairs) *pairs = locPairsN_;
+    if (maxPerCell) *maxPerCell = locMax_;
+  }
+  void locatorFree() override {
+    streamWait();  // a sample in flight still reads the buffers
+    locBuilt_ = false;
+    locX_.alloc(0);
+    locPart_.alloc(0);
+    locScal_.alloc(0);
+    locCnt_.alloc(0);
+    locTmp_.alloc(0);
+    locCounts_.alloc(0);
+    locStarts_.alloc(0);
+    locPairs_.alloc(0);
+    locStage_.alloc(0);
+    locWhere_.alloc(0);
+  }
+  // mmadmm_sample / mmadmm_sample_device
+  void sample(int nQ, const double* Q, int C, const double* u, double* out, int32_t* where, int* counts, bool onDevice,
+              void* stream) override {
+    const char* who = onDevice ? "mmadmm_sample_device" : "mmadmm_sample";
+    singleRankOnly(who);
+    if (!locBuilt_) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": no locator is built (mmadmm_locator_build)");
+    if (nQ == 0) {
+      if (counts) counts[0] = counts[1] = counts[2] = 0;
+      return;
+    }
+    const size_t nq = (size_t)nQ * D, nu = (size_t)nP_ * C, no = (size_t)nQ * C;
+    int cnt[kSampleCountInts];  // the slotted counts (locate_kernels.h), read back when asked for
+    if (!onDevice) {  // staged through the same kernel; the host arrays are done with when the call returns
+      const size_t nqPad = (nq + 1) & ~(size_t)1;  // u and out stay 16-byte aligned behind Q
+      if (locStage_.n < nqPad + nu + no) locStage_.alloc(nqPad + nu + no);
+      if (where && locWhere_.n < (size_t)nQ) locWhere_.alloc(nQ);
+      double *dQ = locStage_.p, *dU = dQ + nqPad, *dO = dU + nu;
+      MMX_HIP(hipMemcpyAsync(dQ, Q, nq * sizeof(double), hipMemcpyHostToDevice, st_));
+      MMX_HIP(hipMemcpyAsync(dU, u, nu * sizeof(double), hipMemcpyHostToDevice, st_));
+      launch_locate_sample<D>(locG_, locStarts_.p, locPairs_.p, locX_.p, F_.p, nQ, dQ, C, dU, dO,
+                              where ? locWhere_.p : nullptr, locCnt_.p, st_);
+      MMX_HIP(hipGetLastError());
+      MMX_HIP(hipMemcpyAsync(out, dO, no * sizeof(double), hipMemcpyDeviceToHost, st_));
+      if (where) MMX_HIP(hipMemcpyAsync(where, locWhere_.p, (size_t)nQ * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+      if (counts) MMX_HIP(hipMemcpyAsync(cnt, locCnt_.p, sizeof cnt, hipMemcpyDeviceToHost, st_));
+      streamWait();
+    } else {
+      if (D == 2 && (((uintptr_t)Q) & 15))
+        throw Error(MMADMM_ERR_INVALID, std::string(who) + ": 2D points must be 16-byte aligned");
+      afterProducer(stream);
+      launch_locate_sample<D>(locG_, locStarts_.p, locPairs_.p, locX_.p, F_.p, nQ, Q, C, u, out, where, locCnt_.p, st_);
+      MMX_HIP(hipGetLastError());
+      if (counts) MMX_HIP(hipMemcpyAsync(cnt, locCnt_.p, sizeof cnt, hipMemcpyDeviceToHost, st_));
+      beforeConsumer(stream);
+      if (counts && stream) streamWait();  // the read-back; without counts the host does not wait
+    }
+    if (counts) sample_sum_counts(cnt, counts);
+  }
+
   // ---- the sliding boundary (slide_kernels.hip)
   // the surface frozen at the current points: faces, the CSR of faces at every node, the sliding
   // nodes and their anchors (each its own node), uploaded once per freeze
@@ -2507,6 +2649,18 @@ class Engine final : public EngineBase {
   std::vector<int32_t> trNbrH_;  // the transfer's face-neighbour table (host copy) and device scratch
   DevBuf<int32_t> trNbr_, trWhere_, trCnt_;
   DevBuf<double> trStage_;
+  // the point locator (locatorBuild): its grid, its own copy of the positions, the box partials, {pair
+  // count, longest list}, counts / cursors, list offsets, lists, scan scratch; the sample's slotted
+  // counts and the host path's staging.  Derived data: no part of the state blob
+  bool locBuilt_ = false;
+  LocateGrid locG_;
+  long long locPairsN_ = 0;
+  int locMax_ = 0;
+  DevBuf<double> locX_, locPart_, locStage_;
+  DevBuf<unsigned long long> locScal_;
+  DevBuf<int> locCounts_, locStarts_, locPairs_, locCnt_;
+  DevBuf<int32_t> locWhere_;
+  DevBuf<unsigned char> locTmp_;
   DevBuf<double> qlE_, qlC_, qlPart_, qlRec_, qlStage_;  // the quality measures' scratch (qualityScratch)
   // the sliding boundary: on / frozen, the frozen surface (host, device), the sliding nodes and their
   // anchors, the slotted figures of a call and of the last step (slStepValid_: a step has written them)
@@ -2934,6 +3088,37 @@ int mmadmm_transfer_device(mmadmm_handle h, const double* d_Xold, const double* 
   return guarded([&] {
     check_transfer("mmadmm_transfer_device", d_Xold, C, d_uold, d_unew);
     eng(h).transfer(d_Xold, d_Xnew, C, d_uold, d_unew, d_where, counts, true, stream);
+  });
+}
+int mmadmm_locator_build(mmadmm_handle h, const double* X, const int* cells) {
+  return guarded([&] { eng(h).locatorBuild(X, cells, false, nullptr); });
+}
+int mmadmm_locator_build_device(mmadmm_handle h, const double* d_X, const int* cells, void* stream) {
+  return guarded([&] { eng(h).locatorBuild(d_X, cells, true, stream); });
+}
+int mmadmm_locator_info(mmadmm_handle h, int cells[3], double* box, long long* pairs, int* max_per_cell) {
+  return guarded([&] { eng(h).locatorInfo(cells, box, pairs, max_per_cell); });
+}
+int mmadmm_locator_free(mmadmm_handle h) {
+  return guarded([&] { eng(h).locatorFree(); });
+}
+static void check_sample(const char* who, int nQ, const double* Q, int C, const double* u, const double* out) {
+  if (C < 1) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": C must be >= 1");
+  if (nQ < 0) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": nQ must be >= 0");
+  if (!u || (nQ > 0 && (!Q || !out))) throw Error(MMADMM_ERR_INVALID, std::string(who) + ": NULL array");
+}
+int mmadmm_sample(mmadmm_handle h, int nQ, const double* Q, int C, const double* u, double* out, int32_t* where,
+                  int* counts) {
+  return guarded([&] {
+    check_sample("mmadmm_sample", nQ, Q, C, u, out);
+    eng(h).sample(nQ, Q, C, u, out, where, counts, false, nullptr);
+  });
+}
+int mmadmm_sample_device(mmadmm_handle h, int nQ, const double* d_Q, int C, const double* d_u, double* d_out,
+                         int32_t* d_where, int* counts, void* stream) {
+  return guarded([&] {
+    check_sample("mmadmm_sample_device", nQ, d_Q, C, d_u, d_out);
+    eng(h).sample(nQ, d_Q, C, d_u, d_out, d_where, counts, true, stream);
   });
 }
 int mmadmm_quality(mmadmm_handle h, const double* X, int source, const double* M, double* q, double* summary) {

@@ -164,6 +164,19 @@ def lib():
     L.mmadmm_transfer_field.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_int_p, c_double_p,
                                         ctypes.c_int, c_double_p, c_double_p, c_int_p, c_int_p]
     L.mmadmm_face_neighbours.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, c_int_p]
+    L.mmadmm_locator_default_cells.argtypes = [ctypes.c_int, ctypes.c_int, c_int_p]
+    L.mmadmm_locator_build.argtypes = [ctypes.c_void_p, c_double_p, c_int_p]
+    L.mmadmm_locator_build_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, c_int_p, ctypes.c_void_p]
+    L.mmadmm_locator_info.argtypes = [ctypes.c_void_p, c_int_p, c_double_p, c_ll_p, c_int_p]
+    L.mmadmm_locator_free.argtypes = [ctypes.c_void_p]
+    L.mmadmm_sample.argtypes = [ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_double_p,
+                                c_int_p, c_int_p]
+    L.mmadmm_sample_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, c_int_p, ctypes.c_void_p]
+    L.mmadmm_sample_field.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_int_p, c_int_p,
+                                      ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_int_p, c_int_p]
+    L.mmadmm_locator_field_info.argtypes = [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_int_p, c_int_p,
+                                            c_int_p, c_double_p, c_ll_p, c_int_p]
     L.mmadmm_quality.argtypes = [ctypes.c_void_p, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_double_p]
     L.mmadmm_quality_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                         ctypes.c_void_p, c_double_p, ctypes.c_void_p]
@@ -435,6 +448,83 @@ def transfer_field(Xold, F, Xnew, u, where=True):
     if where:
         info["where"] = w
     return out.reshape(shape), info
+
+
+SAMPLE_COUNTS = ("inside", "outside", "none")
+
+
+def locator_default_cells(dim, nF):
+    """mmadmm_locator_default_cells: the automatic cells per axis (3 ints, the last 1 in 2D) of a locator
+    over nF simplices."""
+    cells = np.zeros(3, dtype=np.int32)
+    _check(lib().mmadmm_locator_default_cells(int(dim), int(nF), _ip(cells)))
+    return tuple(int(c) for c in cells)
+
+
+def _cells_arg(cells, who):
+    """None, or the caller's cells as 3 int32 (a 2D pair gets its 1)"""
+    if cells is None:
+        return None
+    c = [int(v) for v in cells]
+    if len(c) == 2:
+        c.append(1)
+    if len(c) != 3:
+        raise ValueError(f"{who}: cells must hold 2 or 3 counts")
+    return np.array(c, dtype=np.int32)
+
+
+def _mesh_arrays(X, F, who):
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    F = np.ascontiguousarray(F, dtype=np.int32)
+    if X.ndim != 2 or F.ndim != 2 or F.shape[1] != X.shape[1] + 1:
+        raise ValueError(f"{who}: X nP x D, F nF x (D + 1)")
+    return X, F
+
+
+def _locator_info_dict(D, cells, box, pairs, mx):
+    return {"cells": tuple(int(c) for c in cells), "box": box.reshape(2, D).copy(), "pairs": int(pairs.value),
+            "max_per_cell": int(mx.value)}
+
+
+def locator_field_info(X, F, cells=None):
+    """mmadmm_locator_field_info (host only, no device): what Engine.build_locator reports for the same
+    positions, simplices and cells -> {"cells", "box" (2 x D: lo, hi), "pairs", "max_per_cell"}."""
+    X, F = _mesh_arrays(X, F, "locator_field_info")
+    nP, D = X.shape
+    ca = _cells_arg(cells, "locator_field_info")
+    used, box = np.zeros(3, dtype=np.int32), np.zeros(2 * D)
+    pairs, mx = ctypes.c_longlong(0), ctypes.c_int(0)
+    _check(lib().mmadmm_locator_field_info(D, nP, _dp(X), F.shape[0], _ip(F), _ip(ca) if ca is not None else None,
+                                           _ip(used), _dp(box), ctypes.byref(pairs), ctypes.byref(mx)))
+    return _locator_info_dict(D, used, box, pairs, mx)
+
+
+def sample_field(X, F, Q, u, cells=None, where=True):
+    """mmadmm_sample_field (host only, no device): the piecewise-linear field (node positions X, simplices
+    F, nodal values u: nP or nP x C) evaluated at the points Q (nQ x D) -> (values, info); values is nQ or
+    nQ x C, info holds the counts "inside", "outside", "none" and, unless where is False, "where" (-1
+    none, s >= 0 inside simplex s, -2 - s outside: extrapolated from s).  cells: the locator's cells per
+    axis (None: automatic).  F is used as given: pass Engine.simplices() to reproduce Engine.sample bit
+    for bit."""
+    X, F = _mesh_arrays(X, F, "sample_field")
+    nP, D = X.shape
+    Q = np.ascontiguousarray(Q, dtype=np.float64)
+    if Q.ndim != 2 or Q.shape[1] != D:
+        raise ValueError("sample_field: Q nQ x D")
+    nQ = Q.shape[0]
+    one = np.ndim(u) == 1
+    u2 = _field_2d(u, nP, "sample_field")
+    C = u2.shape[1]
+    ca = _cells_arg(cells, "sample_field")
+    out = np.zeros((nQ, C))
+    w = np.zeros(nQ, dtype=np.int32) if where else None
+    cnt = np.zeros(3, dtype=np.int32)
+    _check(lib().mmadmm_sample_field(D, nP, _dp(X), F.shape[0], _ip(F), _ip(ca) if ca is not None else None, nQ, _dp(Q), C,
+                                     _dp(u2), _dp(out), _ip(w) if where else None, _ip(cnt)))
+    info = {k: int(c) for k, c in zip(SAMPLE_COUNTS, cnt)}
+    if where:
+        info["where"] = w
+    return (out[:, 0].copy() if one else out), info
 
 
 def face_neighbours(F, nP=None):
@@ -1216,6 +1306,89 @@ class Engine:
                                          _dp(u2), _dp(out2), _ip(w) if where else None, _ip(cnt)))
             out = out2.reshape(shape)
         info = {k: int(c) for k, c in zip(TRANSFER_COUNTS, cnt)}
+        if where:
+            info["where"] = w
+        return out, info
+
+    # -- nodal fields at arbitrary points (include/mmadmm.h: mmadmm_locator_build ...)
+    def build_locator(self, X=None, cells=None):
+        """Build, on the device, the cell locator over the engine's simplices at the node positions X (nP x
+        D: a numpy array or a float64 CUDA tensor; None: the engine's current "points") -> {"cells", "box"
+        (2 x D: lo, hi), "pairs", "max_per_cell"}.  cells: the cells per axis (None: automatic).  The
+        locator keeps its own copy of X: later steps, save_state and load_state leave it as it is."""
+        ca = _cells_arg(cells, "build_locator")
+        cp = _ip(ca) if ca is not None else None
+        nx = self.nP * self.dim
+        if X is None:
+            _check(lib().mmadmm_locator_build(self.h, None, cp))
+        elif _is_tensor(X):
+            p, st, j = self._device_arg(X, nx, "build_locator")
+            _check(lib().mmadmm_locator_build_device(self.h, p, cp, st))
+            self._rejoin(j)
+        else:
+            X = np.ascontiguousarray(X, dtype=np.float64)
+            if X.size != nx:
+                raise ValueError(f"build_locator: positions must hold {nx} values")
+            _check(lib().mmadmm_locator_build(self.h, _dp(X), cp))
+        return self.locator_info()
+
+    def locator_info(self):
+        """{"cells", "box", "pairs", "max_per_cell"} of the locator built last (mmadmm_locator_info)."""
+        D = self.dim
+        used, box = np.zeros(3, dtype=np.int32), np.zeros(2 * D)
+        pairs, mx = ctypes.c_longlong(0), ctypes.c_int(0)
+        _check(lib().mmadmm_locator_info(self.h, _ip(used), _dp(box), ctypes.byref(pairs), ctypes.byref(mx)))
+        return _locator_info_dict(D, used, box, pairs, mx)
+
+    def free_locator(self):
+        """Release the locator's device memory; sample is refused until the next build_locator."""
+        _check(lib().mmadmm_locator_free(self.h))
+
+    def sample(self, Q, u, where=False):
+        """The nodal field u (nP or nP x C values at the locator's node positions) evaluated at the points
+        Q (nQ x D), piecewise linearly on the mesh build_locator saw (include/mmadmm.h: mmadmm_sample) ->
+        (values, info); values is nQ or nQ x C.  Numpy arrays go through the host call, float64 CUDA
+        tensors through the _device call on torch's current stream; values (and info["where"], on
+        request) is of the kind given.  info holds the counts "inside", "outside", "none" (reading them
+        waits for the kernel).  where: -1 none (values NaN), s >= 0 inside simplex s, -2 - s outside."""
+        D = self.dim
+        cnt = np.zeros(3, dtype=np.int32)
+        if _is_tensor(u):
+            import torch
+
+            if u.dim() not in (1, 2) or u.shape[0] != self.nP or u.numel() == 0:
+                raise ValueError(f"sample: u must be nP or nP x C values (C >= 1), nP = {self.nP}")
+            C = u.numel() // self.nP
+            if not _is_tensor(Q):
+                raise ValueError("sample: Q and u must both be tensors or both be arrays")
+            if Q.dim() != 2 or Q.shape[1] != D:
+                raise ValueError("sample: Q must be nQ x D")
+            nQ = Q.shape[0]
+            pu, st, j = self._device_arg(u, self.nP * C, "sample")
+            pq, st, j = self._device_arg(Q, nQ * D, "sample")
+            out = torch.empty((nQ,) if u.dim() == 1 else (nQ, C), dtype=torch.float64, device=u.device)
+            w = torch.empty(nQ, dtype=torch.int32, device=u.device) if where else None
+            if j is not None:
+                out.record_stream(j[1])
+                if where:
+                    w.record_stream(j[1])
+            _check(lib().mmadmm_sample_device(self.h, nQ, pq, C, pu, out.data_ptr(), w.data_ptr() if where else None,
+                                              _ip(cnt), st))
+            self._rejoin(j)
+        else:
+            if _is_tensor(Q):
+                raise ValueError("sample: Q and u must both be tensors or both be arrays")
+            one = np.ndim(u) == 1
+            u2 = _field_2d(u, self.nP, "sample")
+            Q = np.ascontiguousarray(Q, dtype=np.float64)
+            if Q.ndim != 2 or Q.shape[1] != D:
+                raise ValueError("sample: Q must be nQ x D")
+            nQ, C = Q.shape[0], u2.shape[1]
+            out2 = np.zeros((nQ, C))
+            w = np.zeros(nQ, dtype=np.int32) if where else None
+            _check(lib().mmadmm_sample(self.h, nQ, _dp(Q), C, _dp(u2), _dp(out2), _ip(w) if where else None, _ip(cnt)))
+            out = out2[:, 0].copy() if one else out2
+        info = {k: int(c) for k, c in zip(SAMPLE_COUNTS, cnt)}
         if where:
             info["where"] = w
         return out, info
